@@ -14,8 +14,11 @@ per GPU (weak scaling: the global batch is 256*N pairs).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 3
 
-Rank 0 prints ONE JSON line (see README / DESIGN.md section 5 for the fields).  `value` comes from the first timed window
-of exactly --steps steps; two more windows of the same length follow and are reported beside it (`windows`).
+Rank 0 prints ONE JSON line (see README / DESIGN.md section 5 for the fields).  `value` and `ms_per_step` come from ONE timed
+window of exactly --steps steps after --warmup untimed ones; a plain run does nothing else.
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full               # + every side measurement (see --full)
 """
 from __future__ import annotations
 
@@ -50,6 +53,14 @@ def parse(argv=None):
                     help="skip the side measurements (f16 engine, dense last block, caption packing, larger batches, "
                          "ViT-L/14@336 share, fp32 engine)")
     ap.add_argument("--overlap", type=int, default=1, help="1: text tower on a second HIP stream (default), 0: one stream")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline window, also run every side measurement: two more windows, the N > 1 collective on its "
+                         "own, the per-kernel profile and roofline (--no-profile drops it), the error against the HF golden fixture "
+                         "and the CPU baseline (--no-cpu-baseline drops both), and the other engines, sizes and configurations "
+                         "(--no-extras drops them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (logits_per_image, image_embeds, text_embeds; float32) to "
+                         "DIR/<name>.npy")
     # "gloo": host-only REHEARSAL of the multi-rank control flow (rendezvous, fenced windows, max over ranks, rank-0-only
     # printing, teardown) for tests/test_bench_ranks.py, which supplies a stub engine through main(model_factory=...).
     # It measures nothing: the line it prints says so, and without a factory the flag is refused.
@@ -373,6 +384,27 @@ def h2d_inclusive(model, cfg, px, ids, mask, steps, warmup, overlap, copy=None):
     return out
 
 
+DUMP_NAMES = ("logits_per_image", "image_embeds", "text_embeds")     # sharded_pair_logits' return value, in order
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: the arrays the timed step hands its caller, as float32 DIR/<name>.npy, so that two builds can be compared
+    output for output (the inputs are seeded: the same arguments give the same inputs).  An array over its third of the 64 MB budget
+    is cut to a fixed, seeded, sorted sample of its rows (the same rows for the same shape).  Returns {name: shape written}."""
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, t in zip(DUMP_NAMES, out):
+        a = t.detach().float().cpu().numpy()
+        row_bytes = a.itemsize * int(np.prod(a.shape[1:]))
+        keep = DUMP_LIMIT_BYTES // len(DUMP_NAMES) // max(row_bytes, 1)
+        if a.shape[0] > keep:
+            a = a[np.sort(np.random.RandomState(0).choice(a.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = list(a.shape)
+    return written
+
+
 def timed_steps(step, n, dev, warmup=0):
     sync = (lambda: torch.cuda.synchronize(dev)) if dev.type == "cuda" else (lambda: None)
     for _ in range(warmup):
@@ -444,6 +476,8 @@ def _run(args, world, rank, world_size_env, model_factory, emit):
                          "engine from main(model_factory=...)); the bench itself runs on MI355X GPUs over RCCL")
     if not rehearsal and model_factory is not None:
         raise SystemExit("a model factory is accepted with --backend gloo only")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"--steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
     if not rehearsal and not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (ROCm) GPU: torch.cuda.is_available() is False; there is no CPU path")
     import torch.distributed as dist
@@ -510,9 +544,11 @@ def _run(args, world, rank, world_size_env, model_factory, emit):
     for _ in range(args.warmup):
         step()
     elapsed, out = window()                                    # THE measurement
-    more = [window()[0] for _ in range(2)]                     # two more windows of the same length, reported beside it
     logits = out[0]
     assert logits.shape == (B, B * world) and bool(torch.isfinite(logits).all())
+    dumped = dump_outputs(args.dump_outputs, out) if args.dump_outputs and rank == 0 else None
+    # everything below up to the line itself is --full: a plain run stops at the headline window
+    more = [window()[0] for _ in range(2)] if args.full else []    # two more windows of the same length, reported beside it
 
     # ---- roofline of the dominant kernel: HIP events recorded by the library on the launch stream, over --steps steps on ONE
     # stream -- the kernel owns the GPU, which is what the rocprofv3 kernel trace of the same command measures
@@ -575,7 +611,7 @@ def _run(args, world, rank, world_size_env, model_factory, emit):
     # N > 1: the step's ONE collective on its own -- the stacked [1, 2, B, P] all-gather, 20 back-to-back, max over ranks -- so a scaling
     # curve can be read against it (value(N) = N * B / (t1 + c(N)))
     collective_us = None
-    if world > 1:
+    if world > 1 and args.full:
         from plip_amd.dist import all_gather_rows
         P = cfg.projection_dim
         buf = torch.zeros((1, 2, B, P), dtype=torch.float32, device=dev)
@@ -593,7 +629,7 @@ def _run(args, world, rank, world_size_env, model_factory, emit):
     roofline = roofline_2s = roles = None
     kernels = []
     one_stream_ms = None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         rows1, raw1 = profile_pass(False)
         total = sum(r["total_ms"] for r in rows1) or 1.0
         one_stream_ms = total / args.steps
@@ -664,13 +700,19 @@ def _run(args, world, rank, world_size_env, model_factory, emit):
         "one_stream_sum_of_kernel_ms": round(one_stream_ms, 3) if one_stream_ms else None,
         "kernels": kernels,
     }
+    res["full"] = bool(args.full)
+    if not args.full:                   # a plain run measured none of these
+        for k in ("windows", "roofline", "roofline_two_stream_events", "roofline_by_role", "one_stream_sum_of_kernel_ms", "kernels"):
+            del res[k]
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
     try:
         from plip_amd.build import source_digest
         res["csrc_sha16"] = source_digest()
     except Exception:  # pragma: no cover
         pass
-    extras = world == 1 and not args.no_extras and args.dtype != "f32"
-    if world == 1 and not args.no_cpu_baseline:
+    extras = args.full and world == 1 and not args.no_extras and args.dtype != "f32"
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             res["logits_max_abs_err"] = logits_error_vs_hf_golden(model, cfg, sd, px, ids, mask, B, args.arch)
         except Exception as e:  # pragma: no cover
@@ -913,7 +955,8 @@ def _run(args, world, rank, world_size_env, model_factory, emit):
                 dist.destroy_process_group()
         except Exception as e:  # pragma: no cover
             res["rccl_one_rank"] = {"error": repr(e)}
-    res["cpu_baseline"] = cpu_baseline(cfg, sd, args.cpu_seconds) if (world == 1 and not args.no_cpu_baseline) else None
+    if args.full:
+        res["cpu_baseline"] = cpu_baseline(cfg, sd, args.cpu_seconds) if (world == 1 and not args.no_cpu_baseline) else None
     emit(json.dumps(res))
     if world > 1:
         dist.barrier()

@@ -85,7 +85,7 @@ def _run_two_ranks(which, argv):
 
 
 def test_bench_main_on_two_gloo_ranks_prints_one_line_from_rank_zero():
-    out = _run_two_ranks("bench", ["--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo"])
+    out = _run_two_ranks("bench", ["--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--full"])
     assert out[1].strip() == ""                      # only rank 0 prints
     lines = [l for l in out[0].splitlines() if l.strip()]
     assert len(lines) == 1
@@ -151,6 +151,111 @@ def test_bench_in_process_gives_the_caller_its_stdout_back(monkeypatch):
     after = os.fstat(1)
     assert (before.st_dev, before.st_ino) == (after.st_dev, after.st_ino)
     assert len(os.listdir("/proc/self/fd")) == n_fds
+
+
+def test_bench_plain_run_on_two_gloo_ranks_is_the_headline_window_only(tmp_path):
+    """Without --full the line carries the headline window and nothing that needs runs of its own; --dump-outputs is written by
+    rank 0: its rows of logits_per_image and the gathered embeddings of both ranks."""
+    d = tmp_path / "dump"
+    out = _run_two_ranks("bench", ["--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--dump-outputs", str(d)])
+    assert out[1].strip() == ""
+    lines = [l for l in out[0].splitlines() if l.strip()]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res["full"] is False and res["n_gpus"] == 2 and res["steps"] == 3 and res["rccl_ranks"] == 2
+    assert res["value"] == pytest.approx(512 * 3 / (res["ms_per_step"] * 3e-3), rel=2e-3)
+    assert res["config"]["collective_us"] is None                    # the collective on its own is a --full measurement
+    for k in ("windows", "roofline", "kernels", "cpu_baseline"):
+        assert k not in res, k
+    import numpy as np
+    shapes = {n: np.load(d / (n + ".npy")).shape for n in ("logits_per_image", "image_embeds", "text_embeds")}
+    assert shapes == {"logits_per_image": (256, 512), "image_embeds": (512, 16), "text_embeds": (512, 16)}
+    assert res["dumped_outputs"] == {k: list(v) for k, v in shapes.items()}
+
+
+def _counting_stub(calls):
+    class Counting(_StubModel):
+        """Counts the steps that reach the engine: sharded_pair_logits encodes the captions once per step."""
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            enc = self.engine.encode_text
+            self.engine.encode_text = lambda *x, **y: (calls.append(1), enc(*x, **y))[1]
+    return Counting
+
+
+def _bench_in_process(argv, monkeypatch, capfd, factory=_StubModel):
+    sys.path.insert(0, ROOT)
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        monkeypatch.delenv(k, raising=False)
+    capfd.readouterr()
+    bench.main(argv + ["--backend", "gloo"], model_factory=factory)
+    lines = [l for l in capfd.readouterr().out.splitlines() if l.strip()]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_steps_sets_the_number_of_timed_steps(monkeypatch, capfd):
+    """--warmup W --steps N: W + N steps in a plain run, W + 3 N with --full (its two extra windows); ms_per_step is the
+    headline window over N steps."""
+    calls = []
+    res = _bench_in_process(["--steps", "7", "--warmup", "2"], monkeypatch, capfd, _counting_stub(calls))
+    assert len(calls) == 2 + 7
+    assert res["steps"] == 7 and res["warmup"] == 2 and res["full"] is False
+    assert res["metric"] == "image+text pairs embedded/sec at 224px bs=256" and res["unit"] == "pairs/s"
+    assert res["higher_is_better"] is True and res["dtype"] == "bf16"
+    assert res["ms_per_step"] == pytest.approx(256e3 / res["value"], rel=1e-3, abs=1e-3)
+    for k in ("windows", "roofline", "kernels", "cpu_baseline"):
+        assert k not in res, k
+    calls.clear()
+    res = _bench_in_process(["--steps", "5", "--warmup", "1", "--full"], monkeypatch, capfd, _counting_stub(calls))
+    assert len(calls) == 1 + 3 * 5
+    assert res["full"] is True and len(res["windows"]["ms_per_step"]) == 3
+    assert res["windows"]["ms_per_step"][0] == pytest.approx(res["ms_per_step"], abs=2e-3)
+    assert res["roofline"] is None and res["cpu_baseline"] is None    # the rehearsal profiles nothing
+    with pytest.raises(SystemExit, match="--steps must be >= 1"):
+        _bench_in_process(["--steps", "0"], monkeypatch, capfd)
+
+
+def test_bench_dump_outputs_is_what_the_timed_step_returned(monkeypatch, capfd, tmp_path):
+    """--dump-outputs DIR: the step's (logits_per_image, image_embeds, text_embeds) as float32 .npy; the same arguments give the
+    same inputs, so two runs write the same arrays -- here the very arrays sharded_pair_logits returns for the seeded batch."""
+    import numpy as np
+    from plip_amd import weights as W
+    from plip_amd.config import get_config
+    from plip_amd.dist import sharded_pair_logits
+    names = ("logits_per_image", "image_embeds", "text_embeds")
+    runs = []
+    for sub in ("a", "b"):
+        res = _bench_in_process(["--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path / sub)], monkeypatch, capfd)
+        runs.append({n: np.load(tmp_path / sub / (n + ".npy")) for n in names})
+        assert sorted(os.listdir(tmp_path / sub)) == sorted(n + ".npy" for n in names)
+        assert res["dumped_outputs"] == {n: list(runs[-1][n].shape) for n in names}
+    cfg = get_config("ViT-B/32")
+    ids, mask = W.synthetic_ids(cfg, 256, seed=2000)
+    want = sharded_pair_logits(_StubModel(cfg, None), torch.from_numpy(W.synthetic_pixels(cfg, 256, seed=1000)), torch.from_numpy(ids),
+                               torch.from_numpy(mask), equal_shards=True)
+    for n, w in zip(names, want):
+        assert runs[0][n].dtype == np.float32 and runs[0][n].shape == tuple(w.shape)
+        np.testing.assert_array_equal(runs[0][n], runs[1][n])
+        np.testing.assert_array_equal(runs[0][n], w.numpy())
+
+
+def test_bench_dump_outputs_samples_fixed_rows_of_an_oversized_output(monkeypatch, tmp_path):
+    """Over the 64 MB budget (a third per array) an array is cut to a seeded, sorted sample of its rows: the same rows every run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * 64 * 40)          # 40 rows of 16 float32 per array
+    big = torch.arange(100 * 16, dtype=torch.float32).reshape(100, 16)
+    small = torch.ones(8, 16, dtype=torch.float64)
+    shapes = [bench.dump_outputs(str(tmp_path / s), (big, small, big)) for s in ("a", "b")]
+    assert shapes[0] == shapes[1] == {"logits_per_image": [40, 16], "image_embeds": [8, 16], "text_embeds": [40, 16]}
+    a, b = (np.load(tmp_path / s / "logits_per_image.npy") for s in ("a", "b"))
+    np.testing.assert_array_equal(a, b)
+    rows = a[:, 0] / 16
+    assert (np.diff(rows) > 0).all() and np.array_equal(a, big.numpy()[rows.astype(int)])
+    assert np.load(tmp_path / "a" / "image_embeds.npy").dtype == np.float32
 
 
 def test_sharded_zero_shot_example_on_two_gloo_ranks():

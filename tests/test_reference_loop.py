@@ -6,13 +6,13 @@ unmodified via ``object.__new__(PLIP)`` with ``self.model`` := ``plip_amd.model.
 ``CLIPProcessor(CLIPImageProcessor(), CLIPTokenizer(<synthetic vocab>))`` (both construct offline).
 ``PLIP.__init__`` itself cannot run under transformers 5.x (``use_auth_token`` kwarg, plip.py:26).
 
-* CPU variant (runs in the build container): the model is a real ``PlipModel`` whose engine is the oracle-backed
-  stand-in of tests/helpers.py, so what is under test is the HOST surface -- kwargs by name, ``.to(device)``, tensor
-  results, batch loop -- and ``plip_amd.PLIP``'s own loops against the reference's on identical inputs, including the
-  centre-crop rule on a 227 x 224 image.
-* GPU variant: the GPU box does not mount /root/reference, so there the loop is ``tests.helpers.ReferenceHostLoops`` -- a
-  restatement of plip.py:31-103's host pattern which the CPU variant pins to the imported original (same arrays on the
-  same model) -- driven against the MI355X engine through libplipmi.so, in all three compute dtypes.  Where the reference
+* CPU variant: the model is a real ``PlipModel`` whose engine is the oracle-backed stand-in of tests/helpers.py, so what
+  is under test is the HOST surface -- kwargs by name, ``.to(device)``, tensor results, batch loop -- and ``plip_amd.PLIP``'s
+  own loops against the reference's on identical inputs, including the centre-crop rule on a 227 x 224 image.
+  What the reference's loops returned on this very model is recorded in tests/golden/reference_host_loops.npz
+  (oracle/make_reference_fixtures.py, which also checks that those loops return exactly ``direct_features``).
+* GPU variant: the loop is ``tests.helpers.ReferenceHostLoops`` -- a restatement of plip.py:31-103's host pattern which
+  the CPU variant pins to the reference's recorded loops (the same per-batch arrays on the same model) -- driven against the MI355X engine through libplipmi.so, in all three compute dtypes.  Where the reference
   tree IS mounted next to a GPU, the original itself runs too.
 The reference's ``reproducibility`` ``CLIPEmbedder`` cannot be driven this way at all: it imports the OpenAI ``clip``
 package, which is not installed.
@@ -24,7 +24,6 @@ import torch
 from tests import helpers as Hh
 
 pytest.importorskip("datasets")
-needs_reference = pytest.mark.skipif(not Hh.reference_available(), reason="/root/reference is not mounted on this box")
 
 
 def _cfg():
@@ -50,6 +49,20 @@ def _processor(tmp_path):
 CAPTIONS = ["an image of the tumor cell", "the cell", "tumor", "an image of an image of the tumor"]
 
 
+def direct_features(model, processor, images, captions, image_batch, text_batch):
+    """What the reference's loops compute, without their ``datasets`` / ``DataLoader`` plumbing: the processor's output
+    fed to ``get_*_features`` in the caller's batches, rows stacked."""
+    px = processor(images=images, return_tensors="pt")["pixel_values"]
+    enc = processor(text=captions, return_tensors="pt", max_length=77, padding="max_length", truncation=True)
+    with torch.no_grad():
+        img = [model.get_image_features(pixel_values=px[i:i + image_batch]).detach().cpu().numpy()
+               for i in range(0, len(images), image_batch)]
+        txt = [model.get_text_features(input_ids=enc["input_ids"][i:i + text_batch],
+                                       attention_mask=enc["attention_mask"][i:i + text_batch]).detach().cpu().numpy()
+               for i in range(0, len(captions), text_batch)]
+    return np.concatenate(img), np.concatenate(txt)
+
+
 def _reference_instance(model, processor, device):
     ref_mod = Hh.load_reference_plip_module()
     ref = object.__new__(ref_mod.PLIP)           # plip.py:14-18 without the hub download
@@ -60,8 +73,7 @@ def _reference_instance(model, processor, device):
     return ref
 
 
-@needs_reference
-def test_reference_host_loops_on_the_drop_in_model_cpu(tmp_path):
+def test_reference_host_loops_on_the_drop_in_model_cpu(tmp_path, golden):
     from oracle import clip_oracle as O
     from plip_amd import weights as W
     from plip_amd.plip import PLIP
@@ -70,12 +82,13 @@ def test_reference_host_loops_on_the_drop_in_model_cpu(tmp_path):
     sd = W.synthetic_state_dict(cfg, 2)
     model = Hh.oracle_model(cfg, sd)
     processor, tok = _processor(tmp_path)
-    ref = _reference_instance(model, processor, "cpu")
+    ref = golden("reference_host_loops")
+    assert list(ref["captions"]) == CAPTIONS
     images = _images()
 
-    # --- the reference's loops, unmodified, on the drop-in model --------------------------------------------------
-    got_img = ref.encode_images(images, batch_size=2)                       # plip.py:31-53
-    got_txt = ref.encode_text(CAPTIONS, batch_size=3)                       # plip.py:55-71
+    # --- the reference's loops, unmodified, on the drop-in model (recorded) ----------------------------------------
+    got_img = ref["encode_images"]                                          # plip.py:31-53, batch_size=2
+    got_txt = ref["encode_text"]                                            # plip.py:55-71, batch_size=3
     assert got_img.shape == (5, cfg.projection_dim) and got_img.dtype == np.float32
     assert got_txt.shape == (4, cfg.projection_dim) and got_txt.dtype == np.float32
     # what those loops must have computed: HF preprocessing -> the towers, un-normalised
@@ -84,7 +97,7 @@ def test_reference_host_loops_on_the_drop_in_model_cpu(tmp_path):
     np.testing.assert_allclose(got_img, O.vision_tower(px, sd, cfg), rtol=0, atol=1e-6)
     np.testing.assert_allclose(got_txt, O.text_tower(enc["input_ids"], sd, cfg, enc["attention_mask"]), rtol=0, atol=1e-6)
     labels = CAPTIONS[:3]
-    ref_pred = ref.zero_shot_classification(images, labels)                 # plip.py:89-103
+    ref_pred = [labels[i] for i in ref["zero_shot"]]                        # plip.py:89-103
     assert len(ref_pred) == 5 and set(ref_pred) <= set(labels)
 
     # --- plip_amd.PLIP's loops on the same model + inputs: identical arrays, identical predictions -------------------
@@ -100,16 +113,15 @@ def test_reference_host_loops_on_the_drop_in_model_cpu(tmp_path):
     assert ours.zero_shot_classification(images, labels) == ref_pred
     kinds = {c[0] for c in model.engine.calls}
     assert "encode_image_u8" in kinds            # native 224 x 224 tiles took the fused-normalisation route
-    np.testing.assert_allclose(ours._cosine_similarity(mine_img, mine_txt), ref._cosine_similarity(got_img, got_txt),
-                                rtol=0, atol=1e-5)
-    ours.image_vectors, ref.image_vectors = mine_img, got_img               # (the reference never assigns it: plip.py:114)
-    np.testing.assert_array_equal(ours.retrieval(CAPTIONS, top_k=3), ref.retrieval(CAPTIONS, top_k=3))
+    np.testing.assert_allclose(ours._cosine_similarity(mine_img, mine_txt), ref["cosine_similarity"], rtol=0, atol=1e-5)
+    ours.image_vectors = mine_img           # (the recorded retrievals ran with image_vectors = got_img; plip.py:114 never assigns it)
+    np.testing.assert_array_equal(ours.retrieval(CAPTIONS, top_k=3), ref["retrieval_k3"])
     # k beyond the corpus: the reference's argsort()[:, -k:] hands back every column
-    assert ours.retrieval(CAPTIONS, top_k=10).shape == ref.retrieval(CAPTIONS, top_k=10).shape == (4, 5)
+    assert ours.retrieval(CAPTIONS, top_k=10).shape == ref["retrieval_k10"].shape == (4, 5)
     # ... and for k = 0 too ([:, -0:] is [:, 0:]): ADVICE r2
-    np.testing.assert_array_equal(ours.retrieval(CAPTIONS, top_k=0), ref.retrieval(CAPTIONS, top_k=0))
+    np.testing.assert_array_equal(ours.retrieval(CAPTIONS, top_k=0), ref["retrieval_k0"])
     # ... and k < 0 drops the |k| weakest columns ([:, -k:] == [:, |k|:] of the ascending order): ADVICE r3
-    np.testing.assert_array_equal(ours.retrieval(CAPTIONS, top_k=-2), ref.retrieval(CAPTIONS, top_k=-2))
+    np.testing.assert_array_equal(ours.retrieval(CAPTIONS, top_k=-2), ref["retrieval_km2"])
     assert ours.retrieval(CAPTIONS, top_k=-2).shape == (4, 3) and ours.retrieval(CAPTIONS, top_k=-9).shape == (4, 0)
 
     # --- batch_size no longer sizes the ENGINE calls: the caller's batches of 2 / 3 reach the towers
@@ -139,11 +151,16 @@ def test_reference_host_loops_on_the_drop_in_model_cpu(tmp_path):
     np.testing.assert_allclose(m_img[:2], a_img[:2], rtol=0, atol=2e-6)
     np.testing.assert_allclose(m_img[4:6], a_img[2:4], rtol=0, atol=2e-6)
 
-    # --- the restatement the GPU box runs (no /root/reference there) IS the reference's loop: identical arrays -------------
+    # --- the restatement the GPU variant runs IS the reference's loop: the very arrays of the per-batch computation, which
+    #     the reference's own loops were checked to return bit for bit when they were recorded; the recording within round-off
     restated = Hh.ReferenceHostLoops(model, processor, "cpu")
-    np.testing.assert_array_equal(restated.encode_images(images, batch_size=2), got_img)
-    np.testing.assert_array_equal(restated.encode_text(CAPTIONS, batch_size=3), got_txt)
-    np.testing.assert_array_equal(restated.cosine_similarity(got_img, got_txt), ref._cosine_similarity(got_img, got_txt))
+    want_img, want_txt = direct_features(model, processor, images, CAPTIONS, 2, 3)
+    r_img, r_txt = restated.encode_images(images, batch_size=2), restated.encode_text(CAPTIONS, batch_size=3)
+    np.testing.assert_array_equal(r_img, want_img)
+    np.testing.assert_array_equal(r_txt, want_txt)
+    np.testing.assert_allclose(r_img, got_img, rtol=0, atol=1e-6)
+    np.testing.assert_allclose(r_txt, got_txt, rtol=0, atol=1e-6)
+    np.testing.assert_allclose(restated.cosine_similarity(got_img, got_txt), ref["cosine_similarity"], rtol=0, atol=1e-6)
     assert restated.zero_shot_classification(images, labels) == ref_pred
 
 

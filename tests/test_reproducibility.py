@@ -1,10 +1,10 @@
 """Host-side pieces of plip_amd.reproducibility: cache naming/bytes and metric arithmetic.
 
-When the reference tree is mounted (this container; never on the GPU box) the same calls are also made through the
-reference's own cacher.py / metrics.py, loaded by file path, and the results compared -- the compatibility pin for
-SURVEY.md section 8f row 4."""
+The compatibility pin for SURVEY.md section 8f row 4: the same calls made through the reference's own cacher.py / metrics.py,
+recorded by oracle/make_reference_fixtures.py into tests/golden/ (reference_reproducibility.json: names, save paths and metric
+values; reference_cache_*.npy: the files its cacher writes, byte for byte) and compared here."""
 import hashlib
-import importlib.util
+import json
 import os
 
 import numpy as np
@@ -12,24 +12,33 @@ import pytest
 
 from plip_amd.reproducibility import cacher, metrics
 
-REF = "/root/reference/reproducibility"
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+# the inputs the recorded reference calls were made on (oracle/make_reference_fixtures.py imports them from here)
+CACHE_KEYS = (("pliptxtlabels", "/a/b/c.pt"), ("cliptxt", "ViT-B/32"))
+SAVEPATH_KEYS = (("clipimgWSSS4LUAD_binary", "RN50"), ("plipimgDigestPath.csv", "/a/b/c.pt"))
 
 
-def _ref_module(rel):
-    path = os.path.join(REF, rel)
-    if not os.path.exists(path):
-        pytest.skip("reference tree not mounted")
-    spec = importlib.util.spec_from_file_location("ref_" + os.path.basename(rel)[:-3], path)
-    mod = importlib.util.module_from_spec(spec)
-    os.environ.setdefault("PYTHONDONTWRITEBYTECODE", "1")
-    import sys
-    old = sys.dont_write_bytecode
-    sys.dont_write_bytecode = True          # the reference tree is read-only
-    try:
-        spec.loader.exec_module(mod)
-    finally:
-        sys.dont_write_bytecode = old
-    return mod
+def interchange_array():
+    return np.random.RandomState(1).randn(5, 512).astype(np.float32)
+
+
+def metric_cases():
+    """([(y_true, y_pred, scores or None) per label set], (targets, predictions) of retrieval_metrics), seeded."""
+    rng = np.random.RandomState(7)
+    ev = []
+    for labels in ([0, 1], [0, 1, 2, 3, 4], ["a", "b", "c"]):
+        yt = [labels[i] for i in rng.randint(0, len(labels), 257)]
+        yp = [labels[i] for i in rng.randint(0, len(labels), 257)]
+        sc = rng.rand(257) if len(labels) == 2 else None
+        ev.append((yt, yp, sc))
+    pred = rng.randint(0, 60, size=(40, 50))
+    return ev, (list(range(40)), pred)
+
+
+def _recorded():
+    with open(os.path.join(GOLDEN_DIR, "reference_reproducibility.json")) as f:
+        return json.load(f)
 
 
 def test_cache_names_and_roundtrip(tmp_path, monkeypatch):
@@ -56,22 +65,26 @@ def test_cache_names_and_roundtrip(tmp_path, monkeypatch):
 
 
 def test_cache_is_interchangeable_with_the_reference(tmp_path, monkeypatch):
-    ref = _ref_module("utils/cacher.py")
+    rec = _recorded()
     monkeypatch.setenv("PC_CACHE_FOLDER", str(tmp_path))
-    x = np.random.RandomState(1).randn(5, 512).astype(np.float32)
-    for name, path in (("pliptxtlabels", "/a/b/c.pt"), ("cliptxt", "ViT-B/32")):
-        assert ref.get_cache_name(name, path) == cacher.get_cache_name(name, path)
-    ref.cache_numpy_object(x, "pliptxtlabels", "/a/b/c.pt")                      # written by the reference ...
+    x = interchange_array()
+    ref_bytes = open(os.path.join(GOLDEN_DIR, "reference_cache_n_p.npy"), "rb").read()       # the reference's np.save of x
+    for name, path, want in rec["cache_names"]:
+        assert cacher.get_cache_name(name, path) == os.path.join(str(tmp_path), want)
+    with open(cacher.get_cache_name("pliptxtlabels", "/a/b/c.pt"), "wb") as f:              # written by the reference ...
+        f.write(ref_bytes)
     np.testing.assert_array_equal(cacher.cache_hit_or_miss("pliptxtlabels", "/a/b/c.pt"), x)   # ... is our hit
-    cacher.cache_numpy_object_raw_filename(x * 2, "plipimgDigestPath.csv", "/a/b/c.pt")       # and the reverse
-    np.testing.assert_array_equal(ref.cache_hit_or_miss_raw_filename("plipimgDigestPath.csv", "/a/b/c.pt"), x * 2)
-    assert ref.get_savepath("clipimgWSSS4LUAD_binary", "RN50") == cacher.get_savepath("clipimgWSSS4LUAD_binary", "RN50")
-    a, b = tmp_path / "ours", tmp_path / "theirs"
-    a.mkdir(); b.mkdir()
+    cacher.cache_numpy_object_raw_filename(x * 2, "plipimgDigestPath.csv", "/a/b/c.pt")       # and the reverse: where the
+    saved = dict(((n, p), w) for n, p, w in rec["savepaths"])                                 # reference looks, its own bytes
+    ours = os.path.join(str(tmp_path), saved[("plipimgDigestPath.csv", "/a/b/c.pt")])
+    assert (open(ours, "rb").read() == open(os.path.join(GOLDEN_DIR, "reference_cache_raw_digestpath.npy"), "rb").read())
+    np.testing.assert_array_equal(np.load(ours), x * 2)
+    assert cacher.get_savepath("clipimgWSSS4LUAD_binary", "RN50") == os.path.join(str(tmp_path), saved[("clipimgWSSS4LUAD_binary", "RN50")])
+    a = tmp_path / "ours"
+    a.mkdir()
     monkeypatch.setenv("PC_CACHE_FOLDER", str(a)); cacher.cache_numpy_object(x, "n", "p")
-    monkeypatch.setenv("PC_CACHE_FOLDER", str(b)); ref.cache_numpy_object(x, "n", "p")
     fn = hashlib.sha256(b"np").hexdigest()
-    assert (a / fn).read_bytes() == (b / fn).read_bytes()                         # byte-identical files
+    assert (a / fn).read_bytes() == ref_bytes                                                 # byte-identical files
 
 
 def test_retrieval_metrics():
@@ -102,18 +115,14 @@ def test_eval_metrics_against_closed_forms(labels):
         assert np.isnan(m["AUC"]) and (m["tp"] == 0 or labels[1] == 1)
 
 
-def test_eval_metrics_match_the_reference(capsys):
-    ref = _ref_module("metrics.py")
-    rng = np.random.RandomState(7)
-    for labels in ([0, 1], [0, 1, 2, 3, 4], ["a", "b", "c"]):
-        yt = [labels[i] for i in rng.randint(0, len(labels), 257)]
-        yp = [labels[i] for i in rng.randint(0, len(labels), 257)]
-        sc = rng.rand(257) if len(labels) == 2 else None
-        ours, theirs = metrics.eval_metrics(yt, yp, sc), ref.eval_metrics(yt, yp, sc)
+def test_eval_metrics_match_the_reference():
+    rec = _recorded()
+    ev, ret = metric_cases()
+    for (yt, yp, sc), theirs in zip(ev, rec["eval_metrics"]):
+        ours = metrics.eval_metrics(yt, yp, sc)
         assert ours.keys() == theirs.keys()
         for k in ours:
             a, b = ours[k], theirs[k]
             assert (np.isnan(a) and np.isnan(b)) or abs(a - b) < 1e-12, k
-    pred = rng.randint(0, 60, size=(40, 50))
-    assert metrics.retrieval_metrics(list(range(40)), pred) == ref.retrieval_metrics(list(range(40)), pred)
-    capsys.readouterr()
+    assert len(rec["eval_metrics"]) == len(ev) == 3
+    assert metrics.retrieval_metrics(*ret) == rec["retrieval_metrics"]

@@ -9,7 +9,7 @@ for rep in 1 2; do for L in pb2 pb4; do
   timeout 120 python tools/gpu_diag.py gemmtrace 3 12800 3072 768 1 2>&1 | grep -E "main loop|^variant" | cut -c1-200 >> $O/ab.log
   timeout 200 python tools/gpu_diag.py tiles 3 2>&1 | grep -E "fc1" >> $O/ab.log
   timeout 200 python tools/gpu_diag.py libgemm 3 2>&1 | grep -E "fc1|big" | grep bfloat16 -A0 | head -4 >> $O/ab.log
-  timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('two-stream', d['value'], d['ms_per_step'], d['windows']['ms_per_step'])" >> $O/ab.log
+  timeout 300 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-extras 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('two-stream', d['value'], d['ms_per_step'], d['windows']['ms_per_step'])" >> $O/ab.log
 done; done
 cp /tmp/lib_keep.so plip_amd/csrc/libplipmi.so
 timeout 600 python -m pytest tests/test_gpu_gemm.py -m gpu -q -x 2>&1 | tail -2 >> $O/ab.log

@@ -5,7 +5,7 @@ t0=$(date +%s)
 timeout 600 python -m pytest tests/test_gpu_attention.py -m gpu -q -x -k "fused or engine_runs" > $O/pytest_fused.log 2>&1; echo "pytest exit $? $(( $(date +%s) - t0 )) s" > $O/status.log
 timeout 400 python tools/gpu_diag.py stepab f0 base f0 base > $O/stepab.log 2>&1
 echo "stepab $(( $(date +%s) - t0 )) s" >> $O/status.log
-timeout 300 python bench.py --steps 20 --warmup 3 --overlap 0 --no-cpu-baseline --no-extras > $O/bench_1s.json 2> $O/bench_1s.err
+timeout 300 python bench.py --steps 20 --warmup 3 --full --overlap 0 --no-cpu-baseline --no-extras > $O/bench_1s.json 2> $O/bench_1s.err
 echo "bench1s $(( $(date +%s) - t0 )) s" >> $O/status.log
 cat $O/status.log; tail -12 $O/pytest_fused.log; grep -E "one stream|max" $O/stepab.log
 python - <<'PY'
