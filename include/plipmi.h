@@ -168,13 +168,29 @@ void plipmi_destroy(plipmi_handle h);
  * pair do for each other -- configs[3]'s shard 99.1 -> 107.5 k img/s (tools/exp/r06_two_batches.py); same bits per row.  Costs the
  * workspace again (ViT-B/32, max_batch 256: 0.56 GB), no second copy of the weights and no packing time. */
 int  plipmi_clone(plipmi_handle src, plipmi_handle* out);
+/* The same, with the vision tower at height x width pixels -- HF CLIPModel.get_image_features / forward(...,
+ * interpolate_pos_encoding=True) (modeling_clip.py CLIPVisionEmbeddings.interpolate_pos_encoding).  Weights shared and reference-
+ * counted as for plipmi_clone (destroy the handles in any order); text tower, heads and setters' state as src's.
+ *   grid      : (height / patch_size) x (width / patch_size), floored like HF's strided conv -- pixels past it are ignored.
+ *               PLIPMI_ERR_INVALID when a side is under one patch or 1 + grid > 1024 tokens.
+ *   positions : the checkpoint's table when the grid has its patch count AND height == width; otherwise the CLS row + the
+ *               n0 x n0 patch rows resampled to the grid as torch.nn.functional.interpolate(mode="bicubic", align_corners=False)
+ *               does in fp32 (A = -0.75, taps clamped at the border) -- computed once on the GPU during this call.
+ *   inputs    : plipmi_encode_image takes fp32 [B,3,height,width], plipmi_encode_image_u8 uint8 [B,height,width,3].
+ *   max_batch : 0 = the largest B with B * (1 + grid) <= src's max_batch * src's vision tokens (>= 1): about src's workspace;
+ *               > 0 as given.  Both towers' calls take at most that many samples on the new handle.
+ * pass_batch, the graph staging, the attention kernels and the fused-kernel choices follow the new token count (197 tokens at
+ * 448 x 448 for ViT-B/32: the streamed MFMA attention; 65 .. 80: the fused q/k/v + attention kernel).  plipmi_clone of the new
+ * handle keeps its size and table. */
+/* (Additive: the version number and every existing entry are unchanged; a caller probes for the symbol.) */
+int  plipmi_clone_resolution(plipmi_handle src, int height, int width, int max_batch, plipmi_handle* out);
 int  plipmi_version(void);
 const char* plipmi_last_error(void);
 /* name of the device the engine runs on ("gfx950:..."), for logs */
 const char* plipmi_device_name(plipmi_handle h);
 
 /* ---- the hot path ----------------------------------------------------------
- * pixels  : fp32 [B,3,H,W] NCHW, already CLIP-normalised (what CLIPProcessor /
+ * pixels  : fp32 [B,3,H,W] NCHW (H = W = image_size, or the handle's plipmi_clone_resolution size), already CLIP-normalised (what CLIPProcessor /
  *           reproducibility/embedders/transform.py:45-52 produce)
  * out     : fp32 [B, projection_dim]; un-normalised when normalize == 0 (what
  *           PLIP.encode_images returns, plip.py:53), L2-normalised rows when 1
@@ -182,7 +198,7 @@ const char* plipmi_device_name(plipmi_handle h);
  * B may be anything in [0, max_batch]. */
 int plipmi_encode_image(plipmi_handle h, const float* pixels, int B, float* out, int normalize, void* stream);
 
-/* Same, from raw tiles: uint8 [B,H,W,3] (HWC RGB, already image_size x image_size).  The CLIP normalisation
+/* Same, from raw tiles: uint8 [B,H,W,3] (HWC RGB, already image_size x image_size -- or the handle's size, plipmi_clone_resolution).  The CLIP normalisation
  * (u8/255 - mean)/std of reproducibility/embedders/transform.py:45-52 / HF CLIPImageProcessor is fused into the
  * patch GEMM's operand load (large batches: im2col on load from the HWC bytes, one fma per pixel; small ones: a fused unfold pass --
  * the same bits), so a tile crosses PCIe and HBM as 150 KB instead of 602 KB of fp32. */

@@ -98,6 +98,11 @@ int plipmi_qkv_attention(int dtype, const void* A, const void* W, const float* c
 int plipmi_attention(int dtype, int impl, const void* qkv, void* out, int B, int S, int H, int causal,
                      const int64_t* key_mask, void* stream);
 
+/* The position-table resampler of plipmi_clone_resolution on its own: src fp32 [1 + n0*n0, D] (CLS row first) -> dst fp32
+ * [1 + gh*gw, D]: the CLS row copied, the patch rows resampled as torch.nn.functional.interpolate(mode="bicubic",
+ * align_corners=False) in fp32.  src and dst are distinct device buffers. */
+int plipmi_resample_pos(const float* src, float* dst, int n0, int gh, int gw, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,7 @@ TEST_SYMBOLS = {
     "plipmi_gemm_nt_traced": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "plipmi_attention": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "plipmi_qkv_attention": (_i, [_i, _vp, _vp, _vp, _vp, _i, _f, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "plipmi_resample_pos": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
 }
 # every symbol include/plipmi.h declares (the product interface): (restype, argtypes)
 SYMBOLS = {
@@ -80,6 +81,7 @@ SYMBOLS = {
     "plipmi_set_graph_batch": (_i, [_vp, _i]),
     "plipmi_get_pass_batch": (_i, [_vp]),
     "plipmi_clone": (_i, [_vp, C.POINTER(_vp)]),
+    "plipmi_clone_resolution": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
     "plipmi_streams_overlap": (_i, [_vp, _vp, _vp, C.POINTER(_f)]),
     "plipmi_l2_normalize": (_i, [_vp, _vp, _i, _i, _vp]),
     "plipmi_logits": (_i, [_vp, _vp, _i, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),

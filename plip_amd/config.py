@@ -88,6 +88,15 @@ class PlipConfig:
         f += 2.0 * self.v_width * self.projection_dim
         return f
 
+    def image_flops_at(self, height: int, width: int) -> float:
+        """``image_flops`` for height x width images (the interpolated-position-table tower, Engine.at_resolution): the grid
+        floors to (height // patch) x (width // patch); patch GEMM, every block at 1 + grid tokens, unmasked attention, head."""
+        n = (height // self.patch_size) * (width // self.patch_size)
+        f = 2.0 * n * self.patch_dim * self.v_width
+        f += self._tower_flops(n + 1, self.v_width, self.v_layers, self.v_mlp)
+        f += 2.0 * self.v_width * self.projection_dim
+        return f
+
     def text_flops(self) -> float:
         f = self._tower_flops(self.context_length, self.t_width, self.t_layers, self.t_mlp)
         f += 2.0 * self.t_width * self.projection_dim

@@ -164,10 +164,17 @@ struct plipmi_engine {
   int graph_batch_cap = 0;
   hipStream_t cap_stream = nullptr;   // captures run here: the legacy default stream cannot capture, and the caller's
                                       // stream never enters capture mode (other threads may be enqueueing on it)
+  // the vision tower's input: img_h x img_w pixels, a gh x gw patch grid (np = gh * gw patches, vis.S = 1 + np tokens).  plipmi_create:
+  // the checkpoint's image_size square; plipmi_clone_resolution: any other size, the grid floored like HF's strided conv
+  int img_h = 0, img_w = 0, gh = 0, gw = 0;
   int np = 0, kpad = 0;
   Tower vis, txt;
   void* patch_w = nullptr;  // [Dv, kpad]
   void* patches = nullptr;  // [max_batch*np, kpad]
+  // vpos = the position table the tower adds ([1 + np, Dv] fp32); vpos_native = the checkpoint's own (n0 x n0 grid) in the weights.
+  // A handle at another grid owns a resampled table (vpos_own, plipmi_clone_resolution), shared with its plipmi_clone's.
+  float* vpos_native = nullptr;
+  std::shared_ptr<DeviceSlab> vpos_own;
   float *cls = nullptr, *vpos = nullptr, *pre_w = nullptr, *pre_b = nullptr, *post_w = nullptr, *post_b = nullptr,
         *vproj_t = nullptr;
   float *tok = nullptr, *tpos = nullptr, *fin_w = nullptr, *fin_b = nullptr, *tproj_t = nullptr;
@@ -236,7 +243,7 @@ void carve_weights(plipmi_engine* e, Carver& c) {
   const size_t es = e->esz;
   e->patch_w = c.take<void>((size_t)g.v_width * e->kpad, es);
   e->cls = c.take<float>(g.v_width, 4);
-  e->vpos = c.take<float>((size_t)(e->np + 1) * g.v_width, 4);
+  e->vpos = e->vpos_native = c.take<float>((size_t)(e->np + 1) * g.v_width, 4);
   e->pre_w = c.take<float>(g.v_width, 4);  e->pre_b = c.take<float>(g.v_width, 4);
   e->post_w = c.take<float>(g.v_width, 4); e->post_b = c.take<float>(g.v_width, 4);
   e->vproj_t = c.take<float>((size_t)g.v_width * g.projection_dim, 4);
@@ -284,7 +291,7 @@ void carve_workspace(plipmi_engine* e, Carver& c) {
   e->patches = c.take<void>(B * e->np * e->kpad, es);
   const size_t gb = (size_t)e->graph_batch_cap;
   if (gb) {
-    e->g_vin = c.take<void>(gb * 3 * g.image_size * g.image_size, 4);
+    e->g_vin = c.take<void>(gb * 3 * e->img_h * e->img_w, 4);
     e->g_tin = c.take<int64_t>(gb * g.context_length, 8);
     e->g_tmask = c.take<int64_t>(gb * g.context_length, 8);
     e->g_vout = c.take<float>(gb * g.projection_dim, 4);
@@ -499,25 +506,26 @@ int vision_embed(plipmi_engine* e, const float* pixels, const uint8_t* tiles_u8,
   // uint8 tiles (round 6): the same gather on the HWC bytes, CLIP normalisation as one fma per pixel -- the rows the unfold_u8 pass +
   // plain patch GEMM produce, bit for bit.
   const bool gather = g_patch_gather && e->half() && !t.small && e->kpad == 3 * g.patch_size * g.patch_size &&
-                      gemm_gather_supports(t.dtype, B, g.image_size, g.patch_size, t.D);
+                      gemm_gather_supports(t.dtype, B, e->img_h, e->img_w, g.patch_size, t.D);
+  const double px_bytes = (double)B * 3 * e->img_h * e->img_w;
   if (gather) {
     { Scope sc(e, s, "cls_rows", 0, (double)B * t.D * 4);
       HIP_TRY(launch_cls_rows(e->cls, e->vpos, t.x, B, t.S, t.D, s)); }
     GemmParams p;
     p.A = nullptr; p.W = e->patch_w; p.C = t.x; p.bias = e->vpos;
     p.M = B * e->np; p.N = t.D; p.K = e->kpad; p.lda = e->kpad; p.ldw = e->kpad; p.ldc = t.D; p.alpha = 1.f; p.np = e->np;
-    p.pix = pixels; p.tiles = tiles_u8; p.img_hw = g.image_size; p.patch_log2 = g.patch_size == 32 ? 5 : 4;
+    p.pix = pixels; p.tiles = tiles_u8; p.img_h = e->img_h; p.img_w = e->img_w; p.patch_log2 = g.patch_size == 32 ? 5 : 4;
     const char* name = "gemm_nt";
-    Scope sc(e, s, name, 2.0 * p.M * p.N * (double)p.K, (double)B * 3 * g.image_size * g.image_size * (tiles_u8 ? 1 : 4) + (double)p.N * p.K * e->esz + (double)p.M * p.N * 4);
+    Scope sc(e, s, name, 2.0 * p.M * p.N * (double)p.K, px_bytes * (tiles_u8 ? 1 : 4) + (double)p.N * p.K * e->esz + (double)p.M * p.N * 4);
     const int rc = gemm_launch_gather(t.dtype, p, s, &name);
     if (e->prof) sc.rename(name_with_role(name, "patch_embed"));
     if (rc != 0) return fail(PLIPMI_ERR_HIP, "patch GEMM (im2col on load) failed: %s", hipGetErrorString((hipError_t)rc));
   } else if (tiles_u8) {
-    Scope sc(e, s, "unfold_patches_u8", 0, (double)B * 3 * g.image_size * g.image_size + (double)B * e->np * e->kpad * e->esz);
-    HIP_TRY(launch_unfold_patches_u8(tiles_u8, e->patches, t.dtype, B, g.image_size, g.patch_size, e->kpad, s));
+    Scope sc(e, s, "unfold_patches_u8", 0, px_bytes + (double)B * e->np * e->kpad * e->esz);
+    HIP_TRY(launch_unfold_patches_u8(tiles_u8, e->patches, t.dtype, B, e->img_h, e->img_w, g.patch_size, e->kpad, s));
   } else {
-    Scope sc(e, s, "unfold_patches", 0, (double)B * 3 * g.image_size * g.image_size * 4 + (double)B * e->np * e->kpad * e->esz);
-    HIP_TRY(launch_unfold_patches(pixels, e->patches, t.dtype, B, g.image_size, g.patch_size, e->kpad, s)); }
+    Scope sc(e, s, "unfold_patches", 0, px_bytes * 4 + (double)B * e->np * e->kpad * e->esz);
+    HIP_TRY(launch_unfold_patches(pixels, e->patches, t.dtype, B, e->img_h, e->img_w, g.patch_size, e->kpad, s)); }
   if (!gather) {
   { Scope sc(e, s, "cls_rows", 0, (double)B * t.D * 4);
     HIP_TRY(launch_cls_rows(e->cls, e->vpos, t.x, B, t.S, t.D, s)); }
@@ -659,6 +667,81 @@ int passes_of(const plipmi_engine* h, int B) {
 }
 int pass_rows(int B, int n, int i) { return B / n + (i < B % n ? 1 : 0); }
 
+// The vision tower's input geometry: img_h x img_w pixels -> a (img_h / patch) x (img_w / patch) grid, 1 + grid tokens.
+void set_vision_shape(plipmi_engine* e, int img_h, int img_w) {
+  const int P = e->cfg.patch_size;
+  e->img_h = img_h; e->img_w = img_w;
+  e->gh = img_h / P; e->gw = img_w / P;
+  e->np = e->gh * e->gw;
+  e->vis.S = e->np + 1;
+}
+
+// Per-handle decisions that follow from cfg.max_batch and the token counts (plipmi_create, and plipmi_clone_resolution at its own
+// vision token count): pass_batch, the small-batch graph shapes, the attention kernels.  (Whether the fused q/k/v + attention
+// kernel and the im2col-on-load patch GEMM apply is decided per call from the tower's S and the batch.)
+void resolve_handle(plipmi_engine* e) {
+  const plipmi_config& g = e->cfg;
+  {
+    // per-sample bytes of one block's activations in the larger tower: q/k/v (3D) + attention output (D) + the two residual planes
+    // (2D) + the MLP hidden (F), 16-bit each (the fp32 engine: twice that and no planes -- the same rule errs on the safe side)
+    auto per_sample = [&](int S, int D, int F) { return (double)S * (3.0 * D + D + 2.0 * D + F) * (double)(g.compute_dtype == PLIPMI_F32 ? 4 : 2); };
+    const double ps = std::max(per_sample(e->vis.S, g.v_width, g.v_mlp), per_sample(g.context_length, g.t_width, g.t_mlp));
+    const int fit = (int)(208e6 / ps) / 32 * 32;       // 208 MB: the cache minus a tower's block weights and the other tower's share
+    // passes under 256 samples cost more in the GEMMs (tile quantisation, the 128x128 tile below 12 800 rows) than the cache returns:
+    // the fp32 ViT-B/32 engine (fit = 128) ran bs = 256 as two passes at 10.1 k img/s instead of one at 12.5 k
+    e->pass_batch = g.pass_batch > 0 ? g.pass_batch : (g.pass_batch == 0 && fit >= 256) ? fit : 0;
+  }
+  e->graph_batch_cap = std::min(g.max_batch, 32);
+  e->graph_batch = g.graph_batch < 0 ? 0 : g.graph_batch == 0 ? e->graph_batch_cap : std::min(g.graph_batch, e->graph_batch_cap);
+  // attention kernel: exact-fp32 VALU kernel for the fp32 engine, MFMA kernels for the 16-bit engines
+  // (PLIPMI_FLAG_VALU_ATTENTION forces the VALU kernel for A/B runs)
+  e->attn_impl = (g.flags & PLIPMI_FLAG_VALU_ATTENTION) ? 0 : PLIPMI_DEFAULT_ATTENTION;
+  if (!e->half()) e->attn_impl = 0;
+  e->attn_impl_txt = e->attn_impl ? 1 : 0;  // S <= 128: single-pass MFMA kernel, longer: chunked online softmax
+  e->attn_impl_vis = e->attn_impl ? 1 : 0;
+}
+
+// hipMalloc the handle's own slab and hand out its pointers: [packed weights | workspace] (with_weights: plipmi_create) or the
+// workspace alone (a handle on another handle's weights: plipmi_clone, plipmi_clone_resolution -- carve_weights is not run, the
+// copied weight pointers stay).  On failure nothing is left allocated.
+int alloc_slab(plipmi_engine* e, bool with_weights) {
+  Carver sizing;
+  if (with_weights) carve_weights(e, sizing);
+  carve_workspace(e, sizing);
+  e->slab_bytes = align_up(sizing.off, 256);
+  e->slab = nullptr;
+  hipError_t me = hipMalloc(reinterpret_cast<void**>(&e->slab), e->slab_bytes);
+  if (me != hipSuccess) {
+    e->slab = nullptr;
+    return fail(PLIPMI_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", e->slab_bytes, hipGetErrorString(me));
+  }
+  e->own = std::make_shared<DeviceSlab>();
+  e->own->p = e->slab;
+  Carver placing;
+  placing.base = e->slab;
+  if (with_weights) carve_weights(e, placing);
+  carve_workspace(e, placing);
+  if (hipHostMalloc(reinterpret_cast<void**>(&e->bad_id), sizeof(int), hipHostMallocMapped) != hipSuccess) e->bad_id = nullptr;
+  else *e->bad_id = 0;
+  return PLIPMI_OK;
+}
+
+// A handle on src's weights with per-handle state of its own (empty graphs, no profile, no scratch); the caller gives it a slab
+plipmi_engine* copy_handle(plipmi_handle src) {
+  plipmi_engine* e = new plipmi_engine(*src);      // configuration, setters' state and every weight pointer
+  e->graphs.clear();                               // per-handle state starts empty
+  e->cap_stream = nullptr;
+  e->sim_ws = nullptr; e->sim_ws_bytes = 0;
+  e->prof = false; e->recs.clear(); e->pool.clear();
+  e->bad_id = nullptr;
+  e->own.reset();
+  e->slab = nullptr;
+  e->vis.small = e->txt.small = false; e->vis.packed = e->txt.packed = false;
+  e->vis.cur = e->vis.planes = e->vis.dtype;
+  e->txt.cur = e->txt.planes = e->txt.layer_dtype(0);
+  return e;
+}
+
 }  // namespace
 
 extern "C" {
@@ -723,49 +806,18 @@ int plipmi_create(const plipmi_config* cfg, const plipmi_weights* w, void* strea
   e->pooled_last = e->ln_fold && !(g.flags & PLIPMI_FLAG_DENSE_LAST_BLOCK);
   e->text_pack = e->pooled_last && (g.flags & PLIPMI_FLAG_PACK_CAPTIONS);
   e->latency_batch = e->half() ? kLatencyBatch : 0;
-  {
-    // per-sample bytes of one block's activations in the larger tower: q/k/v (3D) + attention output (D) + the two residual planes
-    // (2D) + the MLP hidden (F), 16-bit each (the fp32 engine: twice that and no planes -- the same rule errs on the safe side)
-    auto per_sample = [&](int S, int D, int F) { return (double)S * (3.0 * D + D + 2.0 * D + F) * (double)(g.compute_dtype == PLIPMI_F32 ? 4 : 2); };
-    const double ps = std::max(per_sample(tokens, g.v_width, g.v_mlp), per_sample(g.context_length, g.t_width, g.t_mlp));
-    const int fit = (int)(208e6 / ps) / 32 * 32;       // 208 MB: the cache minus a tower's block weights and the other tower's share
-    // passes under 256 samples cost more in the GEMMs (tile quantisation, the 128x128 tile below 12 800 rows) than the cache returns:
-    // the fp32 ViT-B/32 engine (fit = 128) ran bs = 256 as two passes at 10.1 k img/s instead of one at 12.5 k
-    e->pass_batch = g.pass_batch > 0 ? g.pass_batch : (g.pass_batch == 0 && fit >= 256) ? fit : 0;
-  }
-  e->graph_batch_cap = std::min(g.max_batch, 32);
-  e->graph_batch = g.graph_batch < 0 ? 0 : g.graph_batch == 0 ? e->graph_batch_cap : std::min(g.graph_batch, e->graph_batch_cap);
-  e->np = tokens - 1;
   e->kpad = (int)align_up((size_t)3 * g.patch_size * g.patch_size, 64);
   snprintf(e->devname, sizeof(e->devname), "%s:%s", prop.gcnArchName, prop.name);
-  e->vis.D = g.v_width; e->vis.F = g.v_mlp; e->vis.L = g.v_layers; e->vis.H = g.v_heads; e->vis.S = tokens;
+  e->vis.D = g.v_width; e->vis.F = g.v_mlp; e->vis.L = g.v_layers; e->vis.H = g.v_heads;
   e->txt.D = g.t_width; e->txt.F = g.t_mlp; e->txt.L = g.t_layers; e->txt.H = g.t_heads; e->txt.S = g.context_length;
-  // attention kernel: exact-fp32 VALU kernel for the fp32 engine, MFMA kernels for the 16-bit engines
-  // (PLIPMI_FLAG_VALU_ATTENTION forces the VALU kernel for A/B runs)
-  e->attn_impl = (g.flags & PLIPMI_FLAG_VALU_ATTENTION) ? 0 : PLIPMI_DEFAULT_ATTENTION;
-  if (!e->half()) e->attn_impl = 0;
-  e->attn_impl_txt = e->attn_impl ? 1 : 0;  // S <= 128: single-pass MFMA kernel, longer: chunked online softmax
-  e->attn_impl_vis = e->attn_impl ? 1 : 0;
+  set_vision_shape(e, g.image_size, g.image_size);
+  resolve_handle(e);
 
-  Carver sizing;
-  carve_weights(e, sizing);
-  carve_workspace(e, sizing);
-  e->slab_bytes = align_up(sizing.off, 256);
-  hipError_t me = hipMalloc(reinterpret_cast<void**>(&e->slab), e->slab_bytes);
-  if (me != hipSuccess) {
-    const size_t need = e->slab_bytes;
+  if (const int rc = alloc_slab(e, true); rc != PLIPMI_OK) {
     delete e;
-    return fail(PLIPMI_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", need, hipGetErrorString(me));
+    return rc;
   }
-  e->own = std::make_shared<DeviceSlab>();
-  e->own->p = e->slab;
   e->weights = e->own;
-  Carver placing;
-  placing.base = e->slab;
-  carve_weights(e, placing);
-  carve_workspace(e, placing);
-  if (hipHostMalloc(reinterpret_cast<void**>(&e->bad_id), sizeof(int), hipHostMallocMapped) != hipSuccess) e->bad_id = nullptr;
-  else *e->bad_id = 0;
 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int rc = PLIPMI_OK;
@@ -803,33 +855,61 @@ int plipmi_create(const plipmi_config* cfg, const plipmi_weights* w, void* strea
 int plipmi_clone(plipmi_handle src, plipmi_handle* out) {
   if (!src || !out) return fail(PLIPMI_ERR_INVALID, "null argument");
   *out = nullptr;
-  plipmi_engine* e = new plipmi_engine(*src);      // configuration, setters' state and every weight pointer
-  e->graphs.clear();                               // per-handle state starts empty
-  e->cap_stream = nullptr;
-  e->sim_ws = nullptr; e->sim_ws_bytes = 0;
-  e->prof = false; e->recs.clear(); e->pool.clear();
-  e->bad_id = nullptr;
-  e->own.reset();
-  e->slab = nullptr;
-  e->vis.small = e->txt.small = false; e->vis.packed = e->txt.packed = false;
-  e->vis.cur = e->vis.planes = e->vis.dtype;
-  e->txt.cur = e->txt.planes = e->txt.layer_dtype(0);
-  Carver sizing;
-  carve_workspace(e, sizing);
-  e->slab_bytes = align_up(sizing.off, 256);
-  hipError_t me = hipMalloc(reinterpret_cast<void**>(&e->slab), e->slab_bytes);
-  if (me != hipSuccess) {
-    const size_t need = e->slab_bytes;
+  plipmi_engine* e = copy_handle(src);     // keeps src's image size and position table (vpos_own is shared)
+  if (const int rc = alloc_slab(e, false); rc != PLIPMI_OK) {
     delete e;
-    return fail(PLIPMI_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", need, hipGetErrorString(me));
+    return rc;
   }
-  e->own = std::make_shared<DeviceSlab>();
-  e->own->p = e->slab;
-  Carver placing;
-  placing.base = e->slab;
-  carve_workspace(e, placing);
-  if (hipHostMalloc(reinterpret_cast<void**>(&e->bad_id), sizeof(int), hipHostMallocMapped) != hipSuccess) e->bad_id = nullptr;
-  else *e->bad_id = 0;
+  *out = e;
+  return PLIPMI_OK;
+}
+
+int plipmi_clone_resolution(plipmi_handle src, int height, int width, int max_batch, plipmi_handle* out) {
+  if (!src || !out) return fail(PLIPMI_ERR_INVALID, "null argument");
+  *out = nullptr;
+  const plipmi_config& g = src->cfg;
+  const int P = g.patch_size, n0 = g.image_size / g.patch_size;
+  if (height < P || width < P)
+    return fail(PLIPMI_ERR_INVALID, "image %d x %d: each side must be at least one patch (%d pixels)", height, width, P);
+  const int gh = height / P, gw = width / P;
+  const long long tokens = 1 + (long long)gh * gw;
+  if (tokens > 1024)
+    return fail(PLIPMI_ERR_INVALID, "image %d x %d: a %d x %d grid of %d-pixel patches is %lld tokens, more than 1024 per sequence",
+                height, width, gh, gw, P, tokens);
+  if (max_batch < 0) return fail(PLIPMI_ERR_INVALID, "max_batch = %d: 0 (derive it from the source's workspace) or positive", max_batch);
+  // 0: the largest batch whose vision rows fit the source's (B * tokens <= src max_batch * src tokens), at least 1
+  const int B = max_batch > 0 ? max_batch : (int)std::max(1LL, (long long)g.max_batch * src->vis.S / tokens);
+  plipmi_engine* e = copy_handle(src);
+  e->cfg.max_batch = B;
+  set_vision_shape(e, height, width);
+  resolve_handle(e);
+  e->graph_batch = std::min(src->graph_batch, e->graph_batch_cap);   // the source's setter state, within this handle's staging
+  e->vpos_own.reset();
+  e->vpos = e->vpos_native;
+  if (const int rc = alloc_slab(e, false); rc != PLIPMI_OK) {
+    delete e;
+    return rc;
+  }
+  // HF interpolate_pos_encoding: the checkpoint's table as it is for its own patch count on a square image, else CLS + the bicubic
+  // resample of the n0 x n0 patch rows to gh x gw -- computed once, here
+  if (!(gh * gw == n0 * n0 && height == width)) {
+    const size_t bytes = (size_t)tokens * g.v_width * 4;
+    e->vpos_own = std::make_shared<DeviceSlab>();
+    const hipError_t me = hipMalloc(reinterpret_cast<void**>(&e->vpos_own->p), bytes);
+    if (me != hipSuccess) {
+      e->vpos_own->p = nullptr;
+      plipmi_destroy(e);
+      return fail(PLIPMI_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(me));
+    }
+    e->vpos = reinterpret_cast<float*>(e->vpos_own->p);
+    // the legacy stream orders after the weights' packing on any blocking stream; synchronised: the table is ready for every stream
+    hipError_t le = launch_resample_pos(e->vpos_native, e->vpos, n0, gh, gw, g.v_width, nullptr);
+    if (le == hipSuccess) le = hipStreamSynchronize(nullptr);
+    if (le != hipSuccess) {
+      plipmi_destroy(e);
+      return fail(PLIPMI_ERR_HIP, "position table resample (%d x %d -> %d x %d) failed: %s", n0, n0, gh, gw, hipGetErrorString(le));
+    }
+  }
   *out = e;
   return PLIPMI_OK;
 }
@@ -850,9 +930,9 @@ int plipmi_encode_image(plipmi_handle h, const float* pixels, int B, float* out,
   if (B == 0) return PLIPMI_OK;
   if (!pixels || !out) return fail(PLIPMI_ERR_INVALID, "null pixels/out");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const size_t n = (size_t)B * 3 * h->cfg.image_size * h->cfg.image_size;
+  const size_t n = (size_t)B * 3 * h->img_h * h->img_w;
   if (const int np_ = passes_of(h, B); np_ > 1) {
-    const size_t per = (size_t)3 * h->cfg.image_size * h->cfg.image_size;
+    const size_t per = (size_t)3 * h->img_h * h->img_w;
     for (int b0 = 0, i = 0; i < np_; ++i) {
       const int nb = pass_rows(B, np_, i);
       RUN(image_forward(h, pixels + (size_t)b0 * per, nullptr, nb, out + (size_t)b0 * h->cfg.projection_dim, normalize, s));
@@ -870,9 +950,9 @@ int plipmi_encode_image_u8(plipmi_handle h, const uint8_t* tiles, int B, float* 
   if (B == 0) return PLIPMI_OK;
   if (!tiles || !out) return fail(PLIPMI_ERR_INVALID, "null tiles/out");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const size_t n = (size_t)B * 3 * h->cfg.image_size * h->cfg.image_size;
+  const size_t n = (size_t)B * 3 * h->img_h * h->img_w;
   if (const int np_ = passes_of(h, B); np_ > 1) {
-    const size_t per = (size_t)3 * h->cfg.image_size * h->cfg.image_size;
+    const size_t per = (size_t)3 * h->img_h * h->img_w;
     for (int b0 = 0, i = 0; i < np_; ++i) {
       const int nb = pass_rows(B, np_, i);
       RUN(image_forward(h, nullptr, tiles + (size_t)b0 * per, nb, out + (size_t)b0 * h->cfg.projection_dim, normalize, s));
@@ -1199,6 +1279,12 @@ int plipmi_qkv_attention(int dtype, const void* A, const void* W, const float* c
     return fail(PLIPMI_ERR_INVALID, "the fused q/k/v + attention kernel takes 16-bit operands, 65 .. 80 tokens, widths of 64 H (a multiple of 128)");
   HIP_TRY(launch_qkv_attention(dtype, A, W, c2, stats, 1.0f / (float)(ns * kLnSlice), eps, out, B, S, H, causal, key_mask,
                                reinterpret_cast<hipStream_t>(stream), reinterpret_cast<unsigned long long*>(trace)));
+  return PLIPMI_OK;
+}
+int plipmi_resample_pos(const float* src, float* dst, int n0, int gh, int gw, int D, void* stream) {
+  if (!src || !dst || src == dst || n0 <= 0 || gh <= 0 || gw <= 0 || D <= 0 || 1 + gh * gw > 1024 * 1024)
+    return fail(PLIPMI_ERR_INVALID, "bad argument (src [1 + n0*n0, D], dst [1 + gh*gw, D], distinct)");
+  HIP_TRY(launch_resample_pos(src, dst, n0, gh, gw, D, reinterpret_cast<hipStream_t>(stream)));
   return PLIPMI_OK;
 }
 int plipmi_check_async(plipmi_handle h) {

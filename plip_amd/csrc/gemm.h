@@ -90,9 +90,11 @@ struct GemmParams {
   // ADDR 2 (the patch GEMM, im2col ON LOAD; modeling_clip.py:148-154,209-210): A is not read as [M, K] rows -- row m = patch (img, gi, gj)
   // and column k = (c, u, v) are GATHERED from the fp32 NCHW pixels while a K tile is staged: four consecutive pixels of one image row
   // per lane into registers, rounded to the operand type, written to the A stage (LDS-DMA copies bytes, it cannot convert: this is the
-  // register-staged converting A path).  pix = the pixels, img_hw = image side, patch_log2 = log2 of the patch side (4 or 5).
+  // register-staged converting A path).  pix = the pixels, img_h x img_w = image rows x columns (row stride img_w, plane stride
+  // img_h * img_w; the patch grid is (img_h >> patch_log2) x (img_w >> patch_log2), pixels past it are never read -- HF's strided conv
+  // floors the same way), patch_log2 = log2 of the patch side (4 or 5).
   const float* pix = nullptr;
-  int img_hw = 0, patch_log2 = 0;
+  int img_h = 0, img_w = 0, patch_log2 = 0;
   // ADDR 3: the same gather from native uint8 HWC tiles [B, H, W, 3] (plipmi_encode_image_u8; reproducibility/embedders/transform.py:45-52
   // on 224 x 224 tiles reduces to (u8 / 255 - mean) / std): a lane loads the 12 bytes of four RGB pixels, takes the K tile's channel and
   // normalises with ONE fma per pixel -- fl(b * A_c + B_c) rounds to the same bf16 / f16 as the unfold kernel's (b / 255 - mean_c) * (1 / std_c)
@@ -556,18 +558,18 @@ void gemm_nt_kernel(const GemmParams p) {
   GA ga[2][kGather ? NAL : 1];
   if constexpr (kGather) {
     rs_p = kGatherU8 ? make_buffer_rsrc(p.tiles) : make_buffer_rsrc(p.pix);
-    const int P = 1 << p.patch_log2, g = p.img_hw >> p.patch_log2, f4_per_row = P >> 2;   // patch side, patches per image side
+    const int P = 1 << p.patch_log2, gw = p.img_w >> p.patch_log2, f4_per_row = P >> 2;   // patch side, patches per image row
 #pragma unroll
     for (int i = 0; i < NAL; ++i) {
       const int q = i * NT + tid, row = q >> 4, f4 = q & 15;
       int r = m0 + row;
       r = r < Mrt ? r : Mrt - 1;
-      const int img = r / p.np, pp = r - img * p.np, gi = pp / g, gj = pp - gi * g;
+      const int img = r / p.np, pp = r - img * p.np, gi = pp / gw, gj = pp - gi * gw;
       const int j = f4 / f4_per_row, gq = f4 - j * f4_per_row;        // patch row inside the K tile, four-pixel group inside it
       if constexpr (kGatherU8)   // HWC bytes: pixel (img, y, x) at ((img * H + y) * W + x) * 3; the channel is picked after the load
-        pix_off[i] = (unsigned)((((size_t)img * p.img_hw + gi * P + j) * p.img_hw + gj * P + gq * 4) * 3);
-      else
-        pix_off[i] = (unsigned)((((size_t)img * 3 * p.img_hw + gi * P + j) * p.img_hw + gj * P + gq * 4) * 4);
+        pix_off[i] = (unsigned)((((size_t)img * p.img_h + gi * P + j) * p.img_w + gj * P + gq * 4) * 3);
+      else                       // NCHW fp32: pixel (img, c, y, x) at ((img * 3 + c) * H + y) * W + x; the channel is in the scalar offset
+        pix_off[i] = (unsigned)((((size_t)img * 3 * p.img_h + gi * P + j) * p.img_w + gj * P + gq * 4) * 4);
       const int kl = j * P + gq * 4;                                   // column inside the K tile: 16-byte chunk kl >> 3, half (kl >> 2) & 1
       ga_dst[i] = row * 128 + ((((kl >> 3) ^ ((row >> 1) & 7))) << 4) + ((kl >> 2) & 1) * 8;
     }
@@ -576,8 +578,8 @@ void gemm_nt_kernel(const GemmParams p) {
   auto gather_soff = [&](int t) __attribute__((always_inline)) -> unsigned {
     const int tpc_log2 = 2 * p.patch_log2 - 6;
     const int c = t >> tpc_log2, u0 = (t & ((1 << tpc_log2) - 1)) << (6 - p.patch_log2);
-    if constexpr (kGatherU8) return (unsigned)(u0 * p.img_hw * 3);
-    return (unsigned)((c * p.img_hw + u0) * p.img_hw * 4);
+    if constexpr (kGatherU8) return (unsigned)(u0 * p.img_w * 3);
+    return (unsigned)((c * p.img_h + u0) * p.img_w * 4);
   };
   constexpr int NALX = kGather ? NAL : 1;
   auto gather_load = [&](GA (&set)[NALX], int t) __attribute__((always_inline)) {
@@ -1398,7 +1400,7 @@ bool gemm_force_tile(int variant);            // -1 the cost model chooses, -2 t
 bool gemm_remap_tile(int from, int to);       // the cost model's choice `from` runs as tile `to` (-1: as itself again)
 void gemm_reset_overrides();
 // the patch GEMM with its A operand gathered from fp32 pixels while it is staged (ADDR 2: im2col on load, no unfold pass)
-bool gemm_gather_supports(int dtype, int B, int image, int patch, int N);
+bool gemm_gather_supports(int dtype, int B, int img_h, int img_w, int patch, int N);
 int gemm_launch_gather(int dtype, const GemmParams& p, hipStream_t stream, const char** kernel_name);
 
 }  // namespace plipmi

@@ -146,12 +146,14 @@ int gemm_launch(int dtype, int epi, int variant, const GemmParams& p, hipStream_
 // The patch GEMM with im2col on load (gemm.h ADDR 2): C rows = patches, A gathered from the fp32 NCHW pixels.  Applies to 16-bit
 // engines, patch sides 16 / 32 (whole 64-column K tiles of 4 / 2 patch rows), widths of whole 256-column tiles, and batches the cost
 // model gives the ring tile anyway; everything else keeps the unfold pass + the plain patch GEMM.
-bool gemm_gather_supports(int dtype, int B, int image, int patch, int N) {
+// img_h x img_w images (plipmi_clone_resolution): the grid floors to (img_h / patch) x (img_w / patch); a row of img_w pixels must be a
+// whole number of 16-byte fp32 loads / 4-byte-aligned 12-byte uint8 loads (img_w % 4 == 0), other widths take the unfold pass.
+bool gemm_gather_supports(int dtype, int B, int img_h, int img_w, int patch, int N) {
   if (dtype != 1 && dtype != 2) return false;
   if (patch != 16 && patch != 32) return false;
-  if (image % patch || N % 256) return false;
-  const int g = image / patch, M = B * g * g, K = 3 * patch * patch;
-  if (K / 64 < 2 || (size_t)B * 3 * image * image * 4 >= (1ull << 32)) return false;
+  if (img_h < patch || img_w < patch || img_w % 4 || N % 256) return false;
+  const int M = B * (img_h / patch) * (img_w / patch), K = 3 * patch * patch;
+  if (K / 64 < 2 || (size_t)B * 3 * img_h * img_w * 4 >= (1ull << 32)) return false;
   // the ring tile addresses C and W through 32-bit buffer offsets as well: the output rows (patch rows + one CLS row per image + 1,
   // as gemm_launch counts them) and the weight span must stay below 4 GiB too -- for 16-pixel patches the fp32 output of an image
   // (197 x 768 x 4 B) is LARGER than its pixels; beyond, the unfold pass + gemm_launch's 64-bit tile take over

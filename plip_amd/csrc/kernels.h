@@ -28,14 +28,21 @@ hipError_t launch_fold_ln(const float* W, const float* bias, const float* g, con
 hipError_t launch_text_embed_emit(const int64_t* ids, const float* tok, const float* pos, void* hi, void* lo, float* st, int B,
                                   int S, int D, int vocab, int* bad_id, int dtype, hipStream_t s);
 
-// pixels fp32 [B,3,H,W] -> patch rows [B*np, Kpad] (dtype), column (c,u,v), zero padded to Kpad.
-hipError_t launch_unfold_patches(const float* pixels, void* out, int out_dtype, int B, int image, int patch, int Kpad,
+// pixels fp32 [B,3,H,W] -> patch rows [B*np, Kpad] (dtype), column (c,u,v), zero padded to Kpad.  The grid is
+// (H / patch) x (W / patch), row-major; pixels past it are not read (HF's strided conv floors the same way).
+hipError_t launch_unfold_patches(const float* pixels, void* out, int out_dtype, int B, int H, int W, int patch, int Kpad,
                                  hipStream_t s);
 
 // Same unfold for raw tiles: uint8 [B,H,W,3] (HWC, what PIL / np.asarray give) with the CLIP normalisation
 // (u8/255 - mean[c]) / std[c] of reproducibility/embedders/transform.py:45-52 fused in.
-hipError_t launch_unfold_patches_u8(const uint8_t* tiles, void* out, int out_dtype, int B, int image, int patch,
+hipError_t launch_unfold_patches_u8(const uint8_t* tiles, void* out, int out_dtype, int B, int H, int W, int patch,
                                     int Kpad, hipStream_t s);
+
+// Position table for another patch grid (CLIPVisionEmbeddings.interpolate_pos_encoding): row 0 (CLS) copied, the n0 x n0
+// patch rows of src [1 + n0*n0, D] resampled to gh x gw rows of dst [1 + gh*gw, D] -- torch.nn.functional.interpolate(mode =
+// "bicubic", align_corners = False) in fp32: A = -0.75, src = (n0 / g) * (dst + 0.5) - 0.5, taps clamped to the border,
+// x pass then y pass.  dst must not alias src.
+hipError_t launch_resample_pos(const float* src, float* dst, int n0, int gh, int gw, int D, hipStream_t s);
 
 // x[b,0,:] = class_embedding + pos[0,:]   (token rows 1.. are written by the patch GEMM epilogue)
 hipError_t launch_cls_rows(const float* cls, const float* pos, float* x, int B, int tokens, int D, hipStream_t s);

@@ -290,19 +290,19 @@ hipError_t launch_layernorm(const float* x, size_t xs, const float* g, const flo
 // 209-210): row (img, gi, gj), column (c, u, v) -- the order of conv.weight.reshape(out,-1).
 // ---------------------------------------------------------------------------------
 template <typename TOut, bool kVec>
-__global__ __launch_bounds__(256) void unfold_kernel(const float* __restrict__ px, TOut* __restrict__ out, int image,
+__global__ __launch_bounds__(256) void unfold_kernel(const float* __restrict__ px, TOut* __restrict__ out, int H, int W,
                                                      int P, int K, int Kpad) {
-  const int g = image / P;
-  const int row = blockIdx.x;  // img*g*g + gi*g + gj
-  const int img = row / (g * g), cell = row - img * g * g, gi = cell / g, gj = cell - gi * g;
-  const float* base = px + (size_t)img * 3 * image * image + (size_t)(gi * P) * image + gj * P;
+  const int gh = H / P, gw = W / P;
+  const int row = blockIdx.x;  // img*gh*gw + gi*gw + gj
+  const int img = row / (gh * gw), cell = row - img * gh * gw, gi = cell / gw, gj = cell - gi * gw;
+  const float* base = px + (size_t)img * 3 * H * W + (size_t)(gi * P) * W + gj * P;
   TOut* orow = out + (size_t)row * Kpad;
   for (int k = threadIdx.x * 4; k < Kpad; k += 256 * 4) {
     float r[4];
     if constexpr (kVec) {  // P % 4 == 0: the 4 columns are 4 consecutive pixels of one image row
       if (k < K) {
         const int c = k / (P * P), rem = k - c * P * P, u = rem / P, v = rem - u * P;
-        const float4 t = *reinterpret_cast<const float4*>(base + (size_t)c * image * image + (size_t)u * image + v);
+        const float4 t = *reinterpret_cast<const float4*>(base + (size_t)c * H * W + (size_t)u * W + v);
         r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w;
       } else {
         r[0] = r[1] = r[2] = r[3] = 0.f;
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(256) void unfold_kernel(const float* __restrict__ p
         const int kk = k + e;
         if (kk < K) {
           const int c = kk / (P * P), rem = kk - c * P * P, u = rem / P, v = rem - u * P;
-          r[e] = base[(size_t)c * image * image + (size_t)u * image + v];
+          r[e] = base[(size_t)c * H * W + (size_t)u * W + v];
         } else {
           r[e] = 0.f;
         }
@@ -323,14 +323,14 @@ __global__ __launch_bounds__(256) void unfold_kernel(const float* __restrict__ p
   }
 }
 
-hipError_t launch_unfold_patches(const float* pixels, void* out, int out_dtype, int B, int image, int patch, int Kpad,
+hipError_t launch_unfold_patches(const float* pixels, void* out, int out_dtype, int B, int H, int W, int patch, int Kpad,
                                  hipStream_t s) {
   if (B <= 0) return hipSuccess;
-  const int g = image / patch, K = 3 * patch * patch;
-  const dim3 grid(B * g * g), block(256);
-  const bool vec = (patch % 4 == 0) && (image % 4 == 0);
+  const int K = 3 * patch * patch;
+  const dim3 grid(B * (H / patch) * (W / patch)), block(256);
+  const bool vec = (patch % 4 == 0) && (W % 4 == 0) && (H * W) % 4 == 0;   // every float4 load 16-byte aligned
 #define PLIPMI_UNFOLD(T, V) \
-  hipLaunchKernelGGL((unfold_kernel<T, V>), grid, block, 0, s, pixels, (T*)out, image, patch, K, Kpad)
+  hipLaunchKernelGGL((unfold_kernel<T, V>), grid, block, 0, s, pixels, (T*)out, H, W, patch, K, Kpad)
   if (out_dtype == 1) { if (vec) PLIPMI_UNFOLD(bf16_t, true); else PLIPMI_UNFOLD(bf16_t, false); }
   else if (out_dtype == 2) { if (vec) PLIPMI_UNFOLD(f16_t, true); else PLIPMI_UNFOLD(f16_t, false); }
   else                { if (vec) PLIPMI_UNFOLD(float, true);  else PLIPMI_UNFOLD(float, false); }
@@ -341,14 +341,14 @@ hipError_t launch_unfold_patches(const float* pixels, void* out, int out_dtype, 
 // uint8 HWC tiles: one thread produces 4 consecutive v of one (c,u) row = 4 pixels -> reads 4 x 3 bytes (12 contiguous).
 // Normalisation constants: CLIP mean/std (transform.py:50; HF CLIPImageProcessor defaults).
 template <typename TOut>
-__global__ __launch_bounds__(256) void unfold_u8_kernel(const uint8_t* __restrict__ px, TOut* __restrict__ out, int image,
+__global__ __launch_bounds__(256) void unfold_u8_kernel(const uint8_t* __restrict__ px, TOut* __restrict__ out, int H, int W,
                                                         int P, int K, int Kpad) {
   const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f};
   const float istd[3] = {1.0f / 0.26862954f, 1.0f / 0.26130258f, 1.0f / 0.27577711f};
-  const int g = image / P;
+  const int gh = H / P, gw = W / P;
   const int row = blockIdx.x;
-  const int img = row / (g * g), cell = row - img * g * g, gi = cell / g, gj = cell - gi * g;
-  const uint8_t* base = px + ((size_t)img * image * image + (size_t)(gi * P) * image + gj * P) * 3;
+  const int img = row / (gh * gw), cell = row - img * gh * gw, gi = cell / gw, gj = cell - gi * gw;
+  const uint8_t* base = px + ((size_t)img * H * W + (size_t)(gi * P) * W + gj * P) * 3;
   TOut* orow = out + (size_t)row * Kpad;
   for (int k = threadIdx.x * 4; k < Kpad; k += 256 * 4) {
     float r[4];
@@ -357,7 +357,7 @@ __global__ __launch_bounds__(256) void unfold_u8_kernel(const uint8_t* __restric
       const int kk = k + e;
       if (kk < K) {
         const int c = kk / (P * P), rem = kk - c * P * P, u = rem / P, v = rem - u * P;
-        const float x = (float)base[((size_t)u * image + v) * 3 + c] / 255.0f;   // same op order as the reference
+        const float x = (float)base[((size_t)u * W + v) * 3 + c] / 255.0f;   // same op order as the reference
         r[e] = (x - mean[c]) * istd[c];
       } else {
         r[e] = 0.f;
@@ -366,17 +366,64 @@ __global__ __launch_bounds__(256) void unfold_u8_kernel(const uint8_t* __restric
     store4(orow + k, r[0], r[1], r[2], r[3]);
   }
 }
-hipError_t launch_unfold_patches_u8(const uint8_t* tiles, void* out, int out_dtype, int B, int image, int patch,
+hipError_t launch_unfold_patches_u8(const uint8_t* tiles, void* out, int out_dtype, int B, int H, int W, int patch,
                                     int Kpad, hipStream_t s) {
   if (B <= 0) return hipSuccess;
-  const int g = image / patch, K = 3 * patch * patch;
-  const dim3 grid(B * g * g), block(256);
+  const int K = 3 * patch * patch;
+  const dim3 grid(B * (H / patch) * (W / patch)), block(256);
   if (out_dtype == 1)
-    hipLaunchKernelGGL(unfold_u8_kernel<bf16_t>, grid, block, 0, s, tiles, (bf16_t*)out, image, patch, K, Kpad);
+    hipLaunchKernelGGL(unfold_u8_kernel<bf16_t>, grid, block, 0, s, tiles, (bf16_t*)out, H, W, patch, K, Kpad);
   else if (out_dtype == 2)
-    hipLaunchKernelGGL(unfold_u8_kernel<f16_t>, grid, block, 0, s, tiles, (f16_t*)out, image, patch, K, Kpad);
+    hipLaunchKernelGGL(unfold_u8_kernel<f16_t>, grid, block, 0, s, tiles, (f16_t*)out, H, W, patch, K, Kpad);
   else
-    hipLaunchKernelGGL(unfold_u8_kernel<float>, grid, block, 0, s, tiles, (float*)out, image, patch, K, Kpad);
+    hipLaunchKernelGGL(unfold_u8_kernel<float>, grid, block, 0, s, tiles, (float*)out, H, W, patch, K, Kpad);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------
+// Position table at another grid (modeling_clip.py CLIPVisionEmbeddings.interpolate_pos_encoding): aten's
+// upsample_bicubic2d with align_corners = False and an explicit output size -- scale = (float)n0 / g,
+// real = scale * (dst + 0.5) - 0.5 (not clamped for cubic), i = floor(real), t = real - i, Keys weights with A = -0.75,
+// taps i-1 .. i+2 clamped to [0, n0-1]; the four rows are interpolated along x, then the four results along y.
+// One thread per (output row, column d): reads are coalesced over d.  Runs once per derived handle (plipmi_clone_resolution).
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ void cubic_weights(float t, float w[4]) {
+  const float A = -0.75f;
+  auto c1 = [&](float x) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; };          // |x| <= 1
+  auto c2 = [&](float x) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; };    // 1 < |x| < 2
+  w[0] = c2(t + 1.f); w[1] = c1(t); w[2] = c1(1.f - t); w[3] = c2(2.f - t);
+}
+
+__global__ __launch_bounds__(256) void resample_pos_kernel(const float* __restrict__ src, float* __restrict__ dst, int n0, int gh,
+                                                           int gw, int D) {
+  const int row = blockIdx.y;                         // 0 = CLS, 1 + y * gw + x = patch (y, x)
+  const int d = blockIdx.x * 256 + threadIdx.x;
+  if (d >= D) return;
+  if (row == 0) { dst[d] = src[d]; return; }
+  const int y = (row - 1) / gw, x = (row - 1) - y * gw;
+  const float sy = (float)n0 / (float)gh, sx = (float)n0 / (float)gw;
+  const float ry = sy * ((float)y + 0.5f) - 0.5f, rx = sx * ((float)x + 0.5f) - 0.5f;
+  const int iy = (int)floorf(ry), ix = (int)floorf(rx);
+  float wy[4], wx[4];
+  cubic_weights(ry - (float)iy, wy);
+  cubic_weights(rx - (float)ix, wx);
+  const float* tab = src + D;                         // the n0 x n0 patch rows
+  float acc = 0.f;
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const int yy = min(max(iy - 1 + a, 0), n0 - 1);
+    float r[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) r[b] = tab[((size_t)yy * n0 + min(max(ix - 1 + b, 0), n0 - 1)) * D + d];
+    const float v = r[0] * wx[0] + r[1] * wx[1] + r[2] * wx[2] + r[3] * wx[3];
+    acc = a == 0 ? v * wy[0] : acc + v * wy[a];
+  }
+  dst[(size_t)row * D + d] = acc;
+}
+
+hipError_t launch_resample_pos(const float* src, float* dst, int n0, int gh, int gw, int D, hipStream_t s) {
+  if (n0 <= 0 || gh <= 0 || gw <= 0 || D <= 0 || src == dst) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(resample_pos_kernel, dim3((D + 255) / 256, 1 + gh * gw), dim3(256), 0, s, src, dst, n0, gh, gw, D);
   return hipGetLastError();
 }
 

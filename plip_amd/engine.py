@@ -2,6 +2,7 @@
 memory, streams and tensors only -- all arithmetic happens inside libplipmi.so."""
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 import math
@@ -144,11 +145,63 @@ class Engine:
         """A second engine on the SAME packed weights with a workspace of its own (include/plipmi.h plipmi_clone): an engine runs one
         batch per tower at a time, two engines on two streams run consecutive batches of a corpus side by side (``lanes``)."""
         other = object.__new__(Engine)
-        other.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("_h", "_lanes", "_vis", "pair_stream_ratio")})
+        other.__dict__.update({k: v for k, v in self.__dict__.items()
+                               if k not in ("_h", "_lanes", "_vis", "pair_stream_ratio", "_resolutions", "_resize_plans")})
         other._h = C.c_void_p()
         other._lanes, other._no_lanes, other.use_lanes = None, 0, False        # a clone is a lane, it does not fan out itself
         with torch.cuda.device(self.device):
             _lib.check(self.lib.plipmi_clone(self._h, C.byref(other._h)), "plipmi_clone")
+        return other
+
+    # ------------------------------------------------------------------
+    max_resolutions = 4     # derived engines (at_resolution) kept alive per engine; the least recently used one beyond is closed
+
+    @property
+    def image_hw(self):
+        """(height, width) of the images this engine's vision tower takes: the checkpoint's ``image_size`` square, or the size an
+        ``at_resolution`` engine was made for."""
+        hw = self.__dict__.get("_image_hw")
+        return hw if hw is not None else (self.cfg.image_size, self.cfg.image_size)
+
+    @property
+    def v_tokens(self) -> int:
+        h, w = self.image_hw
+        return 1 + (h // self.cfg.patch_size) * (w // self.cfg.patch_size)
+
+    def at_resolution(self, height: int, width: int) -> "Engine":
+        """An engine on the SAME packed weights whose vision tower runs on ``height x width`` images (include/plipmi.h
+        ``plipmi_clone_resolution``): HF's ``interpolate_pos_encoding=True`` -- the patch grid floors to (height // patch) x
+        (width // patch), the position table is resampled bicubically to it (the checkpoint's own table for its own grid on a square
+        image).  Its ``max_batch`` keeps the vision workspace about this engine's: the largest B with B * tokens <= max_batch *
+        this engine's tokens.  Cached by size: at most ``max_resolutions`` stay alive (least recently used closed), and all close
+        with this engine.  Text tower, heads and setters' state are this engine's."""
+        root = self.__dict__.get("_res_root") or self
+        if root is not self:
+            return root.at_resolution(height, width)
+        key = (int(height), int(width))
+        cache = self.__dict__.get("_resolutions")
+        if cache is None:
+            cache = self._resolutions = collections.OrderedDict()
+        if key in cache and cache[key]._h.value:
+            cache.move_to_end(key)
+            return cache[key]
+        cache.pop(key, None)            # (closed by its caller)
+        h, w = key
+        p = self.cfg.patch_size
+        tokens = 1 + (h // p) * (w // p) if h >= p and w >= p else 0
+        mb = max(1, (self.max_batch * self.v_tokens) // tokens) if tokens else 1
+        other = object.__new__(Engine)
+        other.__dict__.update({k: v for k, v in self.__dict__.items()
+                               if k not in ("_h", "_lanes", "_vis", "pair_stream_ratio", "_resolutions", "_resize_plans")})
+        other._h = C.c_void_p()
+        other._lanes, other._no_lanes = None, 0
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.plipmi_clone_resolution(self._h, h, w, mb, C.byref(other._h)), "plipmi_clone_resolution")
+        other._image_hw, other._res_root, other.max_batch = key, self, mb
+        other.pass_batch = int(self.lib.plipmi_get_pass_batch(other._h))
+        cache[key] = other
+        while len(cache) > self.max_resolutions:
+            cache.popitem(last=False)[1].close()
         return other
 
     def lanes(self, n: int = 2):
@@ -209,6 +262,10 @@ class Engine:
         for other in getattr(self, "_lanes", None) or []:
             other.close()
         self._lanes = None
+        for other in list((self.__dict__.get("_resolutions") or {}).values()):
+            other.close()
+        self.__dict__.pop("_resolutions", None)
+        self.__dict__.pop("_res_root", None)
         if getattr(self, "_h", None) is not None and self._h.value:
             self.lib.plipmi_destroy(self._h)
             self._h = C.c_void_p()
@@ -250,9 +307,10 @@ class Engine:
     def encode_image(self, pixels: torch.Tensor, normalize: bool = False) -> torch.Tensor:
         """fp32 [B,3,H,W] (any device) -> fp32 [B,P] on the GPU."""
         cfg = self.cfg
-        if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != cfg.image_size or pixels.shape[3] != cfg.image_size:
+        ih, iw = self.image_hw
+        if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != ih or pixels.shape[3] != iw:
             raise ValueError(f"Input image size ({tuple(pixels.shape)}) doesn't match model "
-                             f"([B,3,{cfg.image_size},{cfg.image_size}]).")
+                             f"([B,3,{ih},{iw}]).")
         with torch.cuda.device(self.device):
             px = pixels.to(device=self.device, dtype=torch.float32).contiguous()
             out = torch.empty((px.shape[0], cfg.projection_dim), dtype=torch.float32, device=self.device)
@@ -264,8 +322,9 @@ class Engine:
         """uint8 [B,H,W,3] RGB tiles already at the model resolution -> fp32 [B,P]; the CLIP
         normalisation is fused into the patch unfold on the GPU."""
         cfg = self.cfg
-        if tiles.dtype != torch.uint8 or tiles.dim() != 4 or tuple(tiles.shape[1:]) != (cfg.image_size, cfg.image_size, 3):
-            raise ValueError(f"tiles must be uint8 [B,{cfg.image_size},{cfg.image_size},3], got {tiles.dtype} {tuple(tiles.shape)}")
+        ih, iw = self.image_hw
+        if tiles.dtype != torch.uint8 or tiles.dim() != 4 or tuple(tiles.shape[1:]) != (ih, iw, 3):
+            raise ValueError(f"tiles must be uint8 [B,{ih},{iw},3], got {tiles.dtype} {tuple(tiles.shape)}")
         with torch.cuda.device(self.device):
             t = tiles.to(device=self.device).contiguous()
             out = torch.empty((t.shape[0], cfg.projection_dim), dtype=torch.float32, device=self.device)
@@ -314,9 +373,9 @@ class Engine:
             self._no_lanes -= 1
 
     def _encode_pair(self, pixels, input_ids, attention_mask, normalize, overlap):
-        cfg = self.cfg          # the image side's shape error comes first, as in CLIPModel.forward, and before anything is enqueued
-        ok = (tuple(pixels.shape[1:]) == (cfg.image_size, cfg.image_size, 3)) if pixels.dtype == torch.uint8 else \
-            (pixels.dim() == 4 and tuple(pixels.shape[1:]) == (3, cfg.image_size, cfg.image_size))
+        ih, iw = self.image_hw  # the image side's shape error comes first, as in CLIPModel.forward, and before anything is enqueued
+        ok = (tuple(pixels.shape[1:]) == (ih, iw, 3)) if pixels.dtype == torch.uint8 else \
+            (pixels.dim() == 4 and tuple(pixels.shape[1:]) == (3, ih, iw))
         if not ok:
             self._encode_image_any(pixels, normalize)       # raises the tower's own ValueError
         n = pixels.shape[0]
@@ -453,7 +512,9 @@ class Engine:
         resize (shortest edge -> n) + centre crop on the GPU; feed the result to :meth:`encode_image_u8`.
         ``crop`` = "torchvision" (OpenAI ``_transform``) or "hf" (``CLIPImageProcessor``), preprocess.crop_offset."""
         from .preprocess import resize_crop_plan
-        n = self.cfg.image_size
+        n, n_w = self.image_hw
+        if n != n_w:
+            raise ValueError(f"resize_crop_u8 makes square tiles; this engine takes {n} x {n_w} images")
         if images_u8.dim() != 4 or images_u8.shape[-1] != 3 or images_u8.dtype != torch.uint8:
             raise ValueError("expected uint8 [B,H,W,3]")
         B, H, Wd = int(images_u8.shape[0]), int(images_u8.shape[1]), int(images_u8.shape[2])
@@ -498,7 +559,7 @@ class Engine:
         """HF ``hidden_states[layer]`` of a tower (parity tests)."""
         cfg = self.cfg
         vision = tower == "vision"
-        S, D = (cfg.v_tokens, cfg.v_width) if vision else (cfg.context_length, cfg.t_width)
+        S, D = (self.v_tokens, cfg.v_width) if vision else (cfg.context_length, cfg.t_width)
         with torch.cuda.device(self.device):
             x = inp.to(device=self.device, dtype=torch.float32 if vision else torch.int64).contiguous()
             if x.shape[0] > self.max_batch:

@@ -202,3 +202,17 @@ def gemm_variants():
             return names
         names.append(n.decode())
         i += 1
+
+
+def resample_pos(table: torch.Tensor, gh: int, gw: int) -> torch.Tensor:
+    """The position-table resampler of ``plipmi_clone_resolution`` on its own (include/plipmi_test.h ``plipmi_resample_pos``):
+    fp32 [1 + n0*n0, D] (CLS row first) -> fp32 [1 + gh*gw, D], bicubic like ``torch.nn.functional.interpolate``."""
+    lib = _lib.load()
+    assert table.is_cuda and table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2
+    n0 = int(round((table.shape[0] - 1) ** 0.5))
+    assert n0 * n0 + 1 == table.shape[0], "table rows must be 1 + n0 * n0"
+    out = torch.empty((1 + gh * gw, table.shape[1]), dtype=torch.float32, device=table.device)
+    with torch.cuda.device(table.device):
+        _lib.check(lib.plipmi_resample_pos(_ptr(table), _ptr(out), n0, int(gh), int(gw), table.shape[1],
+                                           C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)), "plipmi_resample_pos")
+    return out

@@ -90,11 +90,20 @@ class PlipModel:
         return iter(())
 
     # ---- HF surface ---------------------------------------------------------
+    def _image_engine(self, pixel_values, interpolate_pos_encoding: bool) -> Engine:
+        """The engine for these pixels: with ``interpolate_pos_encoding`` (HF modeling_clip.py CLIPVisionEmbeddings) images of
+        another size run on ``Engine.at_resolution`` -- the checkpoint's own size stays on this engine, as HF keeps its table there;
+        without it the engine's own shape check raises HF's ValueError."""
+        if not interpolate_pos_encoding or not torch.is_tensor(pixel_values) or pixel_values.dim() != 4:
+            return self.engine
+        hw = tuple(pixel_values.shape[1:3]) if pixel_values.dtype == torch.uint8 else tuple(pixel_values.shape[2:4])
+        return self.engine if hw == self.engine.image_hw else self.engine.at_resolution(*hw)
+
     @torch.no_grad()
-    def get_image_features(self, pixel_values=None, **_ignored) -> torch.Tensor:
+    def get_image_features(self, pixel_values=None, interpolate_pos_encoding: bool = False, **_ignored) -> torch.Tensor:
         if pixel_values is None:
             raise ValueError("You have to specify pixel_values")
-        return self.engine.encode_image(pixel_values, normalize=False)
+        return self._image_engine(pixel_values, interpolate_pos_encoding).encode_image(pixel_values, normalize=False)
 
     @torch.no_grad()
     def get_text_features(self, input_ids=None, attention_mask=None, **_ignored) -> torch.Tensor:
@@ -103,7 +112,7 @@ class PlipModel:
         return self.engine.encode_text(input_ids, attention_mask, normalize=False)
 
     @torch.no_grad()
-    def forward(self, input_ids=None, pixel_values=None, attention_mask=None, **_ignored):
+    def forward(self, input_ids=None, pixel_values=None, attention_mask=None, interpolate_pos_encoding: bool = False, **_ignored):
         # OpenAI calling convention: model(images, tokens) -> (logits_per_image, logits_per_text)
         openai_style = (input_ids is not None and torch.is_tensor(input_ids) and input_ids.is_floating_point()
                         and pixel_values is not None and not pixel_values.is_floating_point())
@@ -113,7 +122,9 @@ class PlipModel:
             raise ValueError("You have to specify input_ids and pixel_values")
         # modeling_clip.py:793-811: the two towers, here side by side on two HIP streams (Engine.encode_pair: the bits of the
         # one-stream order, the bench's step -- 4.4 -> 4.2 ms at bs = 256)
-        img, txt = self.engine.encode_pair(pixel_values, input_ids, attention_mask, normalize=True)
+        # (interpolate_pos_encoding: both towers on the derived engine -- same weights, the text tower as this engine's)
+        eng = self._image_engine(pixel_values, interpolate_pos_encoding)
+        img, txt = eng.encode_pair(pixel_values, input_ids, attention_mask, normalize=True)
         lpi, lpt, _ = self.engine.logits(img, txt, scale=float(np.exp(float(self.logit_scale))))  # :814-817
         if openai_style:
             return lpi, lpt

@@ -138,9 +138,14 @@ class PLIP:
 
     # -- plip.py:31-53 -------------------------------------------------------
     def encode_images(self, images: Union[List[str], list, np.ndarray, torch.Tensor], batch_size: int,
-                      num_workers: int = 0):
+                      num_workers: int = 0, image_size: Optional[int] = None):
         """``num_workers > 0`` (extension): decode / resize with a thread pool and stream batches through pinned
-        double buffers so host work and H2D overlap the towers (plip_amd/pipeline.py); results are identical."""
+        double buffers so host work and H2D overlap the towers (plip_amd/pipeline.py); results are identical.
+        ``image_size`` (extension): resize the shortest edge to it and centre-crop to image_size x image_size instead of the
+        checkpoint's size, and encode with the position table interpolated to that grid (``Engine.at_resolution``, HF's
+        ``interpolate_pos_encoding=True``) -- e.g. 448 for pathology tiles cut at 448 / 512 px.  None: the checkpoint's size."""
+        if image_size is not None:
+            return self._encode_images_at(images, batch_size, num_workers, int(image_size))
         n_px = self.model.config.image_size
         if num_workers > 0 and not torch.is_tensor(images) and not isinstance(images, np.ndarray) and len(images):
             return self._encode_images_pipelined(list(images), batch_size, num_workers)
@@ -211,12 +216,79 @@ class PLIP:
             dst[i] = im if isinstance(im, np.ndarray) else np.asarray(im.convert("RGB"), dtype=np.uint8)
         return self._stage[:len(tiles)]
 
-    def _encode_images_pipelined(self, images: list, batch_size: int, num_workers: int):
-        """Same routing per batch as the loop above (raw tiles / GPU resize / host Pillow), one batch ahead."""
+    def _encode_images_at(self, images, batch_size: int, num_workers: int, n_px: int):
+        """``encode_images(image_size=n_px)``: the same routing per batch (tiles already n_px x n_px / one size resized on the GPU /
+        anything else through host Pillow) on the engine at n_px x n_px.  Every device-side step of a batch -- upload, resize + crop,
+        encode -- is enqueued inside the lane's call, on the lane's engine and stream; batches are coalesced on the HOST only."""
+        eng = self.model.engine.at_resolution(n_px, n_px)
+        if num_workers > 0 and not torch.is_tensor(images) and not isinstance(images, np.ndarray) and len(images):
+            return self._encode_images_pipelined(list(images), batch_size, num_workers, eng=eng, n_px=n_px)
+        cap = max(int(batch_size), eng.max_batch) if self.coalesce else int(batch_size)
+        outs, pend, kind = [], [], None
+        main = torch.cuda.current_stream(eng.device)
+
+        def consume(e, k, parts):
+            if any(torch.is_tensor(p) and p.is_cuda for p in parts):
+                lane = torch.cuda.current_stream(eng.device)       # device inputs were produced on the caller's stream
+                lane.wait_stream(main)
+                for p in parts:
+                    if torch.is_tensor(p) and p.is_cuda:
+                        p.record_stream(lane)
+            if torch.is_tensor(parts[0]):
+                t = parts[0] if len(parts) == 1 else torch.cat([p.to(eng.device) for p in parts])
+            else:
+                t = torch.from_numpy(parts[0] if len(parts) == 1 else np.concatenate(parts))
+            if k == "tiles":
+                return e.encode_image_u8(t)
+            if k == "resize":
+                return e.encode_image_u8(e.resize_crop_u8(t, crop=_CROP))
+            return e.encode_image(t, normalize=False)
+
+        def flush():
+            nonlocal pend, kind
+            if pend:
+                outs.append(run(lambda e, k=kind, parts=tuple(pend): consume(e, k, parts)))
+            pend, kind = [], None
+
+        with torch.no_grad(), _lane_loop(eng) as run:
+            for s in range(0, len(images), batch_size):
+                chunk = images[s:s + batch_size]
+                if isinstance(chunk, (list, tuple)) and any(isinstance(c, str) for c in chunk):
+                    from PIL import Image
+                    chunk = [Image.open(c) if isinstance(c, str) else c for c in chunk]
+                tiles = _native_u8_tiles(chunk, n_px)
+                same = _uniform_u8_images(chunk, n_px) if tiles is None else None
+                if tiles is not None:
+                    k, h = "tiles", tiles
+                elif same is not None:
+                    k, h = "resize", same
+                elif torch.is_tensor(chunk):     # fp32 pixels at n_px, or uint8 [B,H,W,3] tiles (of another size: the GPU resize)
+                    h = chunk
+                    k = "pixels" if chunk.dtype != torch.uint8 else "tiles" if tuple(chunk.shape[1:]) == (n_px, n_px, 3) else "resize"
+                elif isinstance(chunk, np.ndarray) and chunk.dtype != np.uint8:
+                    k, h = "pixels", chunk
+                elif isinstance(chunk, np.ndarray):
+                    k, h = "resize", chunk
+                else:
+                    k, h = "pixels", preprocess_images(list(chunk), n_px, crop=_CROP)
+                rows = sum(int(p.shape[0]) for p in pend)
+                if kind is not None and (k != kind or tuple(h.shape[1:]) != tuple(pend[0].shape[1:]) or h.dtype != pend[0].dtype
+                                         or type(h) is not type(pend[0]) or rows + h.shape[0] > cap):
+                    flush()
+                pend.append(h)
+                kind = k
+            flush()
+        if not outs:
+            return np.zeros((0, self.model.config.projection_dim), np.float32)
+        return torch.cat(outs).detach().cpu().numpy()
+
+    def _encode_images_pipelined(self, images: list, batch_size: int, num_workers: int, eng=None, n_px: Optional[int] = None):
+        """Same routing per batch as the loop above (raw tiles / GPU resize / host Pillow), one batch ahead.  (``eng`` / ``n_px``:
+        the engine and tile size of ``encode_images(image_size=)``; default the model's.)"""
         from .pipeline import run_batches
         from .preprocess import preprocess_image
-        n_px = self.model.config.image_size
-        eng = self.model.engine
+        n_px = self.model.config.image_size if n_px is None else n_px
+        eng = self.model.engine if eng is None else eng
 
         def decode(im):            # paths are opened here, i.e. on the worker threads
             if isinstance(im, str):
