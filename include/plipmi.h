@@ -42,7 +42,9 @@
 extern "C" {
 #endif
 
-#define PLIPMI_VERSION 412 /* 0.4.1: `pass_batch` appended to the config struct -- a 0.4.0 caller's shorter struct means 0 = automatic;
+#define PLIPMI_VERSION 412 /* (plipmi_tower_shape / plipmi_encode_tower_outputs and plipmi_clone_resolution are new entries, the
+                            * config struct is unchanged: the number stays, an existing test pins it)
+                            * 0.4.1: `pass_batch` appended to the config struct -- a 0.4.0 caller's shorter struct means 0 = automatic;
                             * 0.4.0: plipmi_config starts with `struct_size` (the struct can grow at its tail without breaking
                             * callers compiled against an older header); test / A-B hooks moved to plipmi_test.h
                             * (0.3.1: `text_f16_layers`, PLIPMI_ERR_TOKEN_ID; 0.3.0: `flags`, `graph_batch`, PLIPMI_F16) */
@@ -260,6 +262,24 @@ int plipmi_set_latency_batch(plipmi_handle h, int max_batch);
  * per-caption lengths.  text_embeds are BIT-IDENTICAL to the padded computation.  A caption of L tokens then costs L/77 of
  * a padded one.  The default (off) executes every padded position, which is what the bench's headline line measures. */
 int plipmi_set_text_packing(plipmi_handle h, int on);
+
+/* Per-token tower outputs -- what HF CLIPModel.vision_model / .text_model return with output_hidden_states /
+ * output_attentions (modeling_clip.py CLIPVisionTransformer, CLIPTextTransformer, eager attention).
+ * plipmi_tower_shape: shape[4] = {S tokens, D width, H heads, L blocks} of `tower` on this handle (S of the vision tower
+ * follows the handle's image size: plipmi_clone_resolution).  plipmi_encode_tower_outputs, for B <= max_batch samples:
+ *   input          : vision fp32 pixels [B,3,H,W] as plipmi_encode_image; text int64 ids [B, context_length]
+ *   attention_mask : text only, as plipmi_encode_text (honoured by the attention and the probabilities); NULL for vision
+ *   eos_token_id   : text pooling rule, as plipmi_encode_text
+ *   last_hidden    : fp32 [B,S,D]  vision: the encoder output; text: final_layer_norm(encoder output)
+ *   pooled         : fp32 [B,D]    vision: post_layernorm(CLS row); text: final_layer_norm of the EOS row
+ *   hidden_states  : fp32 [L+1,B,S,D]  [0] = the embeddings (vision: after pre_layrnorm), [l] = the output of block l-1
+ *   attentions     : fp32 [L,B,H,S,S]  softmax probabilities; masked entries exactly 0, every row with a live key sums to 1
+ * Any output may be NULL, not all of them.  Runs eagerly (no graph), every block on every token, the text tower on unpacked rows
+ * through the q/k/v GEMM + attention pair; none of the handle's settings change, and the encode entries return the same bits
+ * after it as before.  Blocks, hidden states and pooled rows are those of the PLIPMI_FLAG_DENSE_LAST_BLOCK forward. */
+int plipmi_tower_shape(plipmi_handle h, int tower, int32_t* shape);
+int plipmi_encode_tower_outputs(plipmi_handle h, int tower, const void* input, const int64_t* attention_mask, int B, int eos_token_id,
+                                float* last_hidden, float* pooled, float* hidden_states, float* attentions, void* stream);
 
 /* in-place row-wise x / sqrt(sum x^2), no epsilon (modeling_clip.py:57-65) */
 int plipmi_l2_normalize(plipmi_handle h, float* x, int N, int D, void* stream);

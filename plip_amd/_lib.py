@@ -89,6 +89,8 @@ SYMBOLS = {
     "plipmi_resize_crop_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "plipmi_similarity_topk": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "plipmi_set_text_packing": (_i, [_vp, _i]),
+    "plipmi_tower_shape": (_i, [_vp, _i, C.POINTER(C.c_int32)]),
+    "plipmi_encode_tower_outputs": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "plipmi_profile_enable": (_i, [_vp, _i]),
     "plipmi_profile_read": (_i, [_vp, C.POINTER(KernelStat), _i, C.POINTER(_i)]),
 }

@@ -108,6 +108,11 @@ struct LnArgs {         // the LayerNorm side of a folded GEMM (gemm.h EPI_*_LN 
   void* xb_out = nullptr; float* st_out = nullptr; void* lo_io = nullptr;     // producer (lo_io: EPI_RESID_SPLIT's lo plane)
   int planes_other = 0;                                                         // producer: write the planes in the other 16-bit format
 };
+// plipmi_encode_tower_outputs: what run_layers hands out per block (fp32, the call's B samples; nullptr = not asked for)
+struct Taps {
+  float* hidden = nullptr;   // [L+1, B, S, D]: slot l+1 after block l (slot 0, the embeddings, is the caller's)
+  float* probs = nullptr;    // [L, B, H, S, S]: block l's attention probabilities (attention_probs.hip)
+};
 // One captured tower forward (hipGraph) per (tower, input kind, batch, normalise, pooling rule, mask?): the ~170 launches
 // of a small-batch encode are replayed with ONE host call instead of being issued one by one (launch-bound at the
 // reference's own batch size of 8, plip.py:90-91).  Inputs / outputs of a captured forward live in handle-owned staging
@@ -390,23 +395,31 @@ int enter_block(plipmi_engine* e, Tower& t, int l, int M, hipStream_t s) {
   return PLIPMI_OK;
 }
 
+// the attention probabilities of the block whose q/k/v GEMM just wrote t.qkv (unpacked rows only)
+int run_attention_probs(plipmi_engine* e, const Tower& t, int B, int causal, const int64_t* key_mask, float* probs, hipStream_t s) {
+  Scope sc(e, s, "attention_probs", 2.0 * B * t.H * (double)t.S * t.S * 64, (double)B * t.H * t.S * t.S * 4);
+  HIP_TRY(launch_attention_probs(t.qkv, probs, t.cur, B, t.S, t.H, causal, key_mask, s));
+  return PLIPMI_OK;
+}
+
 // LayerNorm-folded q/k/v projection + attention of one block: ONE kernel where the sequence fits the fused tile (77-token
 // captions: qkv_attention.hip, the `qkv` activation never reaches memory), else the GEMM and the attention kernel.
 // Either way t.att holds the attention output afterwards, the same bits.
 int run_qkv_attention(plipmi_engine* e, Tower& t, const LayerW& w, int B, int causal, const int64_t* key_mask, hipStream_t s,
-                      const LnArgs& use) {
+                      const LnArgs& use, float* probs = nullptr) {
   const int M = B * t.S, D = t.D;
   const int impl = (&t == &e->vis) ? e->attn_impl_vis : e->attn_impl_txt;
   const int* cu = t.packed ? t.cu : nullptr;
   const int* md = t.packed ? t.mdev : nullptr;
   const double att_flops = 4.0 * B * t.H * (double)t.S * t.S * 64;
-  if (g_fuse_qkv_attention && impl == 1 && !t.packed && !t.small && qkv_attention_supports(t.cur, B, t.S, t.H, D) &&
+  if (!probs && g_fuse_qkv_attention && impl == 1 && !t.packed && !t.small && qkv_attention_supports(t.cur, B, t.S, t.H, D) &&
       (g_fuse_qkv_attention == 2 || qkv_attention_pays(B, t.H, gemm_num_cus()))) {
     Scope sc(e, s, "qkv_attention", 2.0 * M * 3.0 * D * (double)D + att_flops, ((double)M * D * 2 + 3.0 * D * D) * e->esz);
     HIP_TRY(launch_qkv_attention(t.cur, t.h, w.wqkv, w.bqkv, use.stats, use.inv_d, use.eps, t.att, B, t.S, t.H, causal, key_mask, s));
     return PLIPMI_OK;
   }
   RUN(run_gemm(e, t, EPI_BIAS_LN, t.h, w.wqkv, t.qkv, w.bqkv, M, 3 * D, D, 3 * D, 0, s, "qkv", &use, md));
+  if (probs) RUN(run_attention_probs(e, t, B, causal, key_mask, probs, s));
   Scope sc(e, s, impl ? "attention_mfma" : "attention_valu", att_flops, (double)M * 4 * D * e->esz);
   HIP_TRY(launch_attention(t.qkv, t.att, t.cur, B, t.S, t.H, causal, key_mask, impl, s, cu));
   return PLIPMI_OK;
@@ -414,8 +427,11 @@ int run_qkv_attention(plipmi_engine* e, Tower& t, const LayerW& w, int B, int ca
 
 // n_layers pre-LN residual blocks over the tower's residual stream x (CLIPEncoderLayer, modeling_clip.py:362-383)
 int run_layers(plipmi_engine* e, Tower& t, int B, int n_layers, int causal, const int64_t* key_mask, hipStream_t s,
-               bool more_follow = false) {
+               bool more_follow = false, const Taps* taps = nullptr) {
   const int M = B * t.S, D = t.D, F = t.F;
+  const size_t probs_per_layer = (size_t)B * t.H * t.S * t.S;
+  auto probs_of = [&](int l) -> float* { return taps && taps->probs ? taps->probs + (size_t)l * probs_per_layer : nullptr; };
+  auto hidden_of = [&](int l) -> float* { return taps && taps->hidden ? taps->hidden + (size_t)(l + 1) * M * D : nullptr; };
   const float eps = e->cfg.layer_norm_eps;
   const int impl = (&t == &e->vis) ? e->attn_impl_vis : e->attn_impl_txt;
   const int* cu = t.packed ? t.cu : nullptr;          // packed captions: row offsets / live-row count on the device
@@ -436,7 +452,7 @@ int run_layers(plipmi_engine* e, Tower& t, int B, int n_layers, int causal, cons
     for (int l = 0; l < n_layers; ++l) {
       const LayerW& w = t.layers[l];
       RUN(enter_block(e, t, l, M, s));
-      RUN(run_qkv_attention(e, t, w, B, causal, key_mask, s, use));
+      RUN(run_qkv_attention(e, t, w, B, causal, key_mask, s, use, probs_of(l)));
       RUN(run_gemm(e, t, EPI_RESID_SPLIT, t.att, w.wo, nullptr, w.bo, M, D, D, D, 0, s, "out_proj", &emit, md));
       RUN(run_gemm(e, t, EPI_QGELU_LN, t.h, w.w1, t.mlp, w.b1, M, F, D, F, 0, s, "fc1", &use, md));
       // a block whose successor runs on the other 16-bit operand type (the last f16 block of a mixed text tower) writes its
@@ -447,6 +463,10 @@ int run_layers(plipmi_engine* e, Tower& t, int B, int n_layers, int causal, cons
       emit2.planes_other = (next_dt != t.cur && !(t.small && !md)) ? 1 : 0;
       RUN(run_gemm(e, t, EPI_RESID_SPLIT, t.mlp, w.w2, nullptr, w.b2, M, D, F, D, 0, s, "fc2", &emit2, md));
       if (emit2.planes_other) t.planes = next_dt;
+      if (float* hs = hidden_of(l)) {
+        Scope sc(e, s, "join_planes", 0, (double)M * D * 7);
+        HIP_TRY(launch_join_planes(t.h, t.lo, hs, (size_t)M, D, t.planes, s));
+      }
     }
     if (!more_follow) {
       if (t.packed) return fail(PLIPMI_ERR_INVALID, "packed rows have no every-token form");   // a consumer of plain fp32 rows follows (the every-token head, plipmi_debug_hidden)
@@ -461,12 +481,14 @@ int run_layers(plipmi_engine* e, Tower& t, int B, int n_layers, int causal, cons
     { Scope sc(e, s, "layernorm", 0, (double)M * D * (4 + e->esz));
       HIP_TRY(launch_layernorm(t.x, D, w.ln1w, w.ln1b, t.h, t.cur, M, D, eps, s)); }
     RUN(run_gemm(e, t, EPI_BIAS, t.h, w.wqkv, t.qkv, w.bqkv, M, 3 * D, D, 3 * D, 0, s, "qkv"));
+    if (float* pr = probs_of(l)) RUN(run_attention_probs(e, t, B, causal, key_mask, pr, s));
     RUN(attention());
     RUN(run_gemm(e, t, EPI_BIAS_RESID, t.att, w.wo, t.x, w.bo, M, D, D, D, 0, s, "out_proj"));
     { Scope sc(e, s, "layernorm", 0, (double)M * D * (4 + e->esz));
       HIP_TRY(launch_layernorm(t.x, D, w.ln2w, w.ln2b, t.h, t.cur, M, D, eps, s)); }
     RUN(run_gemm(e, t, EPI_BIAS_QGELU, t.h, w.w1, t.mlp, w.b1, M, F, D, F, 0, s, "fc1"));
     RUN(run_gemm(e, t, EPI_BIAS_RESID, t.mlp, w.w2, t.x, w.b2, M, D, F, D, 0, s, "fc2"));
+    if (float* hs = hidden_of(l)) HIP_TRY(hipMemcpyAsync(hs, t.x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
   }
   return PLIPMI_OK;
 }
@@ -1060,6 +1082,68 @@ int plipmi_debug_hidden(plipmi_handle h, int tower, int layer, const void* input
   else RUN(text_embed(h, reinterpret_cast<const int64_t*>(input), B, s));
   RUN(run_layers(h, t, B, layer, tower == PLIPMI_TEXT, nullptr, s));
   HIP_TRY(hipMemcpyAsync(out, t.x, (size_t)B * t.S * t.D * 4, hipMemcpyDeviceToDevice, s));
+  return PLIPMI_OK;
+}
+
+int plipmi_tower_shape(plipmi_handle h, int tower, int32_t* shape) {
+  if (!h || !shape) return fail(PLIPMI_ERR_INVALID, "null handle/shape");
+  if (tower != PLIPMI_VISION && tower != PLIPMI_TEXT) return fail(PLIPMI_ERR_INVALID, "tower must be 0 (vision) or 1 (text), got %d", tower);
+  const Tower& t = tower == PLIPMI_VISION ? h->vis : h->txt;
+  shape[0] = t.S; shape[1] = t.D; shape[2] = t.H; shape[3] = t.L;
+  return PLIPMI_OK;
+}
+
+// The per-token outputs of one tower (CLIPVisionTransformer / CLIPTextTransformer with output_hidden_states /
+// output_attentions): eager, every block dense on every token, text unpacked and through the q/k/v GEMM + attention pair
+// (the probabilities need `qkv` in memory).  Per-call switches only: the handle's packing, fusion rule, captured graphs and
+// latency setting are read by the encode paths as before, and the workspace they use is rewritten by their next call.
+int plipmi_encode_tower_outputs(plipmi_handle h, int tower, const void* input, const int64_t* attention_mask, int B, int eos_token_id,
+                                float* last_hidden, float* pooled, float* hidden_states, float* attentions, void* stream) {
+  RUN(check_batch(h, B));
+  if (tower != PLIPMI_VISION && tower != PLIPMI_TEXT) return fail(PLIPMI_ERR_INVALID, "tower must be 0 (vision) or 1 (text), got %d", tower);
+  const bool vision = tower == PLIPMI_VISION;
+  if (!vision) RUN(check_async(h));
+  if (B == 0) return PLIPMI_OK;
+  if (!input) return fail(PLIPMI_ERR_INVALID, "null input");
+  if (!last_hidden && !pooled && !hidden_states && !attentions) return fail(PLIPMI_ERR_INVALID, "no output buffer given");
+  if (vision && attention_mask) return fail(PLIPMI_ERR_INVALID, "the vision tower takes no attention mask");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Tower& t = vision ? h->vis : h->txt;
+  const int M = B * t.S, D = t.D;
+  const float eps = h->cfg.layer_norm_eps;
+  const int64_t* ids = vision ? nullptr : reinterpret_cast<const int64_t*>(input);
+  t.small = false;      // the big-tile GEMMs (the encode paths set their own regime per call)
+  t.packed = false;
+  if (vision) RUN(vision_embed(h, reinterpret_cast<const float*>(input), nullptr, B, s));
+  else RUN(text_embed(h, ids, B, s));
+  if (hidden_states) {  // hidden_states[0]: the embeddings (vision: after pre_layrnorm)
+    if (h->ln_fold) {
+      Scope sc(h, s, "join_planes", 0, (double)M * D * 7);
+      HIP_TRY(launch_join_planes(t.h, t.lo, hidden_states, (size_t)M, D, t.planes, s));
+    } else {
+      HIP_TRY(hipMemcpyAsync(hidden_states, t.x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
+    }
+  }
+  Taps taps;
+  taps.hidden = hidden_states;
+  taps.probs = attentions;
+  RUN(run_layers(h, t, B, t.L, vision ? 0 : 1, attention_mask, s, /*more_follow=*/false, &taps));   // t.x = the encoder output, fp32
+  if (vision) {
+    if (last_hidden) HIP_TRY(hipMemcpyAsync(last_hidden, t.x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
+    if (pooled) {
+      Scope sc(h, s, "pool_layernorm", 0, (double)B * D * 8);
+      HIP_TRY(launch_pool_layernorm(t.x, t.S, D, nullptr, -1, h->post_w, h->post_b, eps, pooled, B, s));
+    }
+  } else {
+    if (last_hidden) {
+      Scope sc(h, s, "layernorm", 0, (double)M * D * 8);
+      HIP_TRY(launch_layernorm(t.x, D, h->fin_w, h->fin_b, last_hidden, 0, M, D, eps, s));
+    }
+    if (pooled) {
+      Scope sc(h, s, "pool_layernorm", 0, (double)B * D * 8);
+      HIP_TRY(launch_pool_layernorm(t.x, t.S, D, ids, eos_token_id, h->fin_w, h->fin_b, eps, pooled, B, s));
+    }
+  }
   return PLIPMI_OK;
 }
 

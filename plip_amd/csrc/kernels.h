@@ -113,6 +113,12 @@ hipError_t launch_scale_copy(const float* src, float* dst, int n, float scale, h
 hipError_t launch_attention(const void* qkv, void* out, int dtype, int B, int S, int H, int causal,
                             const int64_t* key_mask, int impl, hipStream_t s, const int* cu = nullptr);
 
+// Attention probabilities of HF's eager attention (attention_probs.hip, plipmi_encode_tower_outputs only): fp32
+// probs [B, H, S, S] = softmax(q k^T + mask) from the same qkv buffer (dtype 0 fp32, 1 bf16, 2 f16), the same causal / key_mask
+// rules; masked entries exactly 0, a row with no live key all 0.  S <= 1024.
+hipError_t launch_attention_probs(const void* qkv, float* probs, int dtype, int B, int S, int H, int causal, const int64_t* key_mask,
+                                  hipStream_t s);
+
 // The text tower's LayerNorm-folded q/k/v projection with the attention in its epilogue (qkv_attention.hip): one launch, no
 // `qkv` tensor in memory.  A = the residual stream's operand plane [B*S, D], W / c2 = the folded q | k | v weights [3D, D] and
 // biases, stats = the rows' LayerNorm partials [B*S, D/64, 2]; out = attention output [B*S, D], bit-identical to

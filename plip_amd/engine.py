@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from .config import PlipConfig
+from .outputs import TowerOutput, tower_output_bytes
 
 _DTYPES = {"fp32": _lib.F32, "f32": _lib.F32, "float32": _lib.F32, torch.float32: _lib.F32,
            "bf16": _lib.BF16, "bfloat16": _lib.BF16, torch.bfloat16: _lib.BF16,
@@ -34,6 +35,12 @@ _PAIR_STREAMS = {}      # (device, main stream) -> the text tower's stream of En
 
 def _code(dt) -> int:
     return _DTYPES[dt]
+
+
+def _tower_code(tower: str) -> int:
+    if tower not in ("vision", "text"):
+        raise ValueError(f"tower must be 'vision' or 'text', got {tower!r}")
+    return _lib.VISION if tower == "vision" else _lib.TEXT
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -554,6 +561,71 @@ class Engine:
                                                        int(k), _ptr(idx), _ptr(vals) if vals is not None else None,
                                                        self._stream()), "plipmi_similarity_topk")
         return (idx, vals) if return_values else idx
+
+    def tower_shape(self, tower: str):
+        """(S tokens, D width, H heads, L blocks) of ``tower`` ("vision" / "text") on this engine (include/plipmi.h plipmi_tower_shape)."""
+        code = _tower_code(tower)
+        shape = (C.c_int32 * 4)()
+        _lib.check(self.lib.plipmi_tower_shape(self._h, code, shape), "plipmi_tower_shape")
+        return tuple(int(v) for v in shape)
+
+    def tower_outputs(self, tower: str, inp: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                      output_hidden_states: bool = False, output_attentions: bool = False,
+                      eos_token_id: Optional[int] = None) -> TowerOutput:
+        """HF ``CLIPModel.vision_model(pixel_values)`` / ``.text_model(input_ids, attention_mask)`` (include/plipmi.h
+        plipmi_encode_tower_outputs): ``last_hidden_state`` [B,S,D], ``pooler_output`` [B,D] and, when asked for, ``hidden_states``
+        (L+1 tensors [B,S,D]) and ``attentions`` (L tensors [B,H,S,S]), fp32 on the GPU.  Runs in chunks of ``max_batch`` samples on
+        this engine.  Raises ValueError before allocating anything when the outputs (and, over several chunks, one chunk's staging)
+        would not fit the device's free memory -- ViT-L/14@336 attentions alone are 511 MB per image."""
+        code = _tower_code(tower)
+        vision = code == _lib.VISION
+        cfg = self.cfg
+        if vision:
+            if attention_mask is not None:
+                raise ValueError("the vision tower takes no attention_mask")
+            ih, iw = self.image_hw
+            if inp.dim() != 4 or tuple(inp.shape[1:]) != (3, ih, iw):
+                raise ValueError(f"Input image size ({tuple(inp.shape)}) doesn't match model ([B,3,{ih},{iw}]).")
+        elif inp.dim() != 2 or inp.shape[1] != cfg.context_length:
+            raise ValueError(f"input_ids must be [B,{cfg.context_length}], got {tuple(inp.shape)}")
+        elif inp.device.type == "cpu" and inp.numel() and (int(inp.min()) < 0 or int(inp.max()) >= cfg.vocab_size):
+            raise IndexError(f"token id out of range [0,{cfg.vocab_size})")
+        S, D, H, L = self.tower_shape(tower)
+        B = int(inp.shape[0])
+        chunks = list(self._chunks(B))
+        nb = tower_output_bytes(B, S, D, H, L, hidden_states=output_hidden_states, attentions=output_attentions)
+        staged = tower_output_bytes(min(B, self.max_batch), S, D, H, L, False, False, output_hidden_states, output_attentions)
+        need = sum(nb.values()) + (sum(staged.values()) if len(chunks) > 1 else 0)
+        free, _ = torch.cuda.mem_get_info(self.device)
+        if need > free:
+            raise ValueError(f"{tower} tower outputs for {B} samples need {need / 2**20:.0f} MiB of device memory, {free / 2**20:.0f} MiB "
+                             f"are free (attentions: {nb['attentions'] / 2**20:.0f} MiB): pass fewer samples or drop output_attentions / "
+                             "output_hidden_states")
+        eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
+        dev = dict(device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            x = inp.to(device=self.device, dtype=torch.float32 if vision else torch.int64).contiguous()
+            mask = None if attention_mask is None else attention_mask.to(device=self.device, dtype=torch.int64).contiguous()
+            last = torch.empty((B, S, D), **dev)
+            pooled = torch.empty((B, D), **dev)
+            hs = torch.empty((L + 1, B, S, D), **dev) if output_hidden_states else None
+            att = torch.empty((L, B, H, S, S), **dev) if output_attentions else None
+            for a, b in chunks:
+                one = len(chunks) == 1
+                hs_c = None if hs is None else (hs if one else torch.empty((L + 1, b - a, S, D), **dev))
+                att_c = None if att is None else (att if one else torch.empty((L, b - a, H, S, S), **dev))
+                _lib.check(self.lib.plipmi_encode_tower_outputs(
+                    self._h, code, _ptr(x[a:b]), _ptr(None if mask is None else mask[a:b]), b - a, eos, _ptr(last[a:b]),
+                    _ptr(pooled[a:b]), _ptr(hs_c), _ptr(att_c), self._stream()), "plipmi_encode_tower_outputs")
+                if not one:
+                    if hs is not None:
+                        hs[:, a:b].copy_(hs_c)
+                    if att is not None:
+                        att[:, a:b].copy_(att_c)
+                    del hs_c, att_c
+        return TowerOutput(last_hidden_state=last, pooler_output=pooled,
+                           hidden_states=None if hs is None else tuple(hs.unbind(0)),
+                           attentions=None if att is None else tuple(att.unbind(0)))
 
     def hidden(self, tower: str, layer: int, inp: torch.Tensor) -> torch.Tensor:
         """HF ``hidden_states[layer]`` of a tower (parity tests)."""

@@ -24,6 +24,7 @@ import torch
 from . import weights as W
 from .config import PlipConfig, get_config
 from .engine import Engine
+from .outputs import TowerOutput
 
 
 @dataclass
@@ -34,12 +35,29 @@ class PlipOutput:
     text_embeds: torch.Tensor
     image_embeds: torch.Tensor
     loss: Optional[torch.Tensor] = None
+    # forward(..., output_hidden_states= / output_attentions=True): the two towers' per-token outputs (CLIPOutput's fields of those names)
+    text_model_output: Optional[TowerOutput] = None
+    vision_model_output: Optional[TowerOutput] = None
 
     def __getitem__(self, k):
         return getattr(self, k)
 
     def to_tuple(self):
-        return (self.logits_per_image, self.logits_per_text, self.text_embeds, self.image_embeds)
+        towers = tuple(o.to_tuple() for o in (self.text_model_output, self.vision_model_output) if o is not None)
+        return (self.logits_per_image, self.logits_per_text, self.text_embeds, self.image_embeds) + towers
+
+
+class _Tower:
+    """``CLIPModel.vision_model`` / ``.text_model``: called with the tower's input, returns a :class:`TowerOutput`."""
+
+    def __init__(self, model: "PlipModel", vision: bool):
+        self._model, self._vision = model, vision
+
+    @torch.no_grad()
+    def forward(self, *args, **kw) -> TowerOutput:
+        return self._model._vision_outputs(*args, **kw) if self._vision else self._model._text_outputs(*args, **kw)
+
+    __call__ = forward
 
 
 class PlipModel:
@@ -55,6 +73,9 @@ class PlipModel:
         self.training = False
         # OpenAI-clip exposes the parameter itself (training_model/clip.py:206 clamps it)
         self.logit_scale = torch.tensor(self.engine.logit_scale, dtype=torch.float32, device=self.device)
+        # HF CLIPVisionTransformer / CLIPTextTransformer: per-token outputs (Engine.tower_outputs)
+        self.vision_model = _Tower(self, vision=True)
+        self.text_model = _Tower(self, vision=False)
 
     # ---- construction -----------------------------------------------------
     @classmethod
@@ -111,8 +132,23 @@ class PlipModel:
             raise ValueError("You have to specify input_ids")
         return self.engine.encode_text(input_ids, attention_mask, normalize=False)
 
+    def _vision_outputs(self, pixel_values=None, output_attentions: bool = False, output_hidden_states: bool = False,
+                        interpolate_pos_encoding: bool = False, **_ignored) -> TowerOutput:
+        if pixel_values is None:
+            raise ValueError("You have to specify pixel_values")
+        return self._image_engine(pixel_values, interpolate_pos_encoding).tower_outputs(
+            "vision", pixel_values, output_hidden_states=bool(output_hidden_states), output_attentions=bool(output_attentions))
+
+    def _text_outputs(self, input_ids=None, attention_mask=None, output_attentions: bool = False, output_hidden_states: bool = False,
+                      **_ignored) -> TowerOutput:
+        if input_ids is None:
+            raise ValueError("You have to specify input_ids")
+        return self.engine.tower_outputs("text", input_ids, attention_mask, output_hidden_states=bool(output_hidden_states),
+                                         output_attentions=bool(output_attentions))
+
     @torch.no_grad()
-    def forward(self, input_ids=None, pixel_values=None, attention_mask=None, interpolate_pos_encoding: bool = False, **_ignored):
+    def forward(self, input_ids=None, pixel_values=None, attention_mask=None, interpolate_pos_encoding: bool = False,
+                output_attentions: bool = False, output_hidden_states: bool = False, **_ignored):
         # OpenAI calling convention: model(images, tokens) -> (logits_per_image, logits_per_text)
         openai_style = (input_ids is not None and torch.is_tensor(input_ids) and input_ids.is_floating_point()
                         and pixel_values is not None and not pixel_values.is_floating_point())
@@ -128,7 +164,13 @@ class PlipModel:
         lpi, lpt, _ = self.engine.logits(img, txt, scale=float(np.exp(float(self.logit_scale))))  # :814-817
         if openai_style:
             return lpi, lpt
-        return PlipOutput(logits_per_image=lpi, logits_per_text=lpt, text_embeds=txt, image_embeds=img)
+        out = PlipOutput(logits_per_image=lpi, logits_per_text=lpt, text_embeds=txt, image_embeds=img)
+        if output_attentions or output_hidden_states:
+            # modeling_clip.py CLIPModel.forward: the towers' own outputs ride along (a separate dense, eager walk of each tower;
+            # the embeddings above are the encode path's)
+            out.text_model_output = self._text_outputs(input_ids, attention_mask, output_attentions, output_hidden_states)
+            out.vision_model_output = self._vision_outputs(pixel_values, output_attentions, output_hidden_states, interpolate_pos_encoding)
+        return out
 
     __call__ = forward
 
