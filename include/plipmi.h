@@ -20,6 +20,8 @@
  *                            image_embeddings.dot(text_embeddings.T); argmax  reproducibility/evaluation/zero_shot/zero_shot.py:12-13
  *   plipmi_topk           <- cosine_sim.argsort()[:, -k:][:, ::-1]            plip.py:78-87, evaluation/retrieval/retrieval.py:13-18
  *   plipmi_similarity_topk<- the same two call sites, fused with the dot product (no [N,N] matrix)
+ *   plipmi_probe_fit      <- SGDClassifier(loss="log_loss", ...).fit(train_x, train_y)   reproducibility/evaluation/linear_probing/linear_classifier.py:18-31
+ *   plipmi_probe_predict  <- classifier.predict(x)                                       linear_classifier.py:32-33
  *
  * Conventions
  *   - plain C, no torch / HIP types in the signatures: device buffers are raw
@@ -86,7 +88,8 @@ enum {
   PLIPMI_ERR_HIP = 2,       /* a HIP runtime call failed */
   PLIPMI_ERR_NODEVICE = 3,  /* no gfx950 device visible */
   PLIPMI_ERR_NOMEM = 4,
-  PLIPMI_ERR_TOKEN_ID = 5   /* an EARLIER plipmi_encode_text on the handle saw a token id outside the vocabulary (below) */
+  PLIPMI_ERR_TOKEN_ID = 5,  /* an EARLIER plipmi_encode_text on the handle saw a token id outside the vocabulary (below) */
+  PLIPMI_ERR_NOT_CONVERGED = 6  /* plipmi_probe_fit stopped at max_iter (or its line search stalled) above gtol; outputs are valid */
 };
 
 typedef struct plipmi_engine* plipmi_handle;
@@ -317,6 +320,40 @@ int plipmi_resize_crop_u8(plipmi_handle h, const uint8_t* src, int B, int H, int
  * plip.py:78-87 for corpora whose [N,N] matrix would not fit. */
 int plipmi_similarity_topk(plipmi_handle h, const float* keys, int Nq, const float* space, int Ns, int D, int k,
                            int64_t* idx, float* vals, void* stream);
+
+/* ---- linear-probe head ---------------------------------------------------------
+ * The reference's third evaluation head (linear_classifier.py): K one-vs-rest logistic problems on cached embeddings,
+ *   f_k(w, b) = (1/N) sum_i c_ik log(1 + exp(-t_ik (x_i.w + b))) + alpha/2 |w|^2,   t_ik = +1 if y_i is problem k's label else -1,
+ * the objective of scikit-learn's SGDClassifier(loss="log_loss", penalty="l2", alpha); the intercept is not regularised.
+ *   X      fp32 [N, D] device, 16-byte aligned, D % 4 == 0, 4 <= D <= 1024
+ *   y      int32 [N] device, class indices.  K >= 2: problem k's positive label is k.  K == 1 is the two-class problem: positive
+ *          label 1.  A label that is no problem's positive one is a negative everywhere (the host checks the range).
+ *   pos_w, neg_w  fp32 [K] device: c_ik for the positives / negatives of problem k (class_weight="balanced": N / (C count_k) and 1;
+ *          two classes: the two class weights)
+ *   WB     fp32 [K, D + 1] device: row k = w_k, then b_k.  1 <= K <= PLIPMI_PROBE_MAX_K.
+ * plipmi_probe_fit minimises every f_k from the point in WB_inout (zeros = scikit-learn's start) and leaves the result there:
+ * L-BFGS (10 pairs) per problem with a backtracking line search on the host, one fused loss-and-gradient pass over X per
+ * evaluation for all K trial points (csrc/probe.hip: fp32 MFMA, X read once per pass, fixed-order reductions -- the same inputs
+ * give the same bits).  Unlike every other entry it SYNCHRONISES the stream (once per evaluation).  A problem stops when
+ * the infinity norm of its gradient is <= gtol; PLIPMI_ERR_NOT_CONVERGED when one has not got there after max_iter iterations --
+ * WB_inout and info_out then hold the best point found.  This is a converged, deterministic solver of the reference's objective,
+ * not its early-stopped sequential SGD: there is no seed.  Scratch lives on the handle (freed by plipmi_destroy), outside the
+ * tower workspace.
+ * plipmi_probe_predict: decision fp32 [N, K] = X W^T + b (optional, may be NULL) and pred int32 [N] = the first arg-max over
+ * the K problems; K == 1: 1 if the decision value is > 0 else 0.  Enqueues only. */
+#define PLIPMI_PROBE_MAX_K 64
+typedef struct plipmi_probe_info {
+  int32_t iterations;    /* accepted L-BFGS steps of the problem that took most */
+  int32_t evaluations;   /* loss-and-gradient passes over X */
+  int32_t converged;     /* problems that met gtol (== K on PLIPMI_OK) */
+  int32_t reserved;
+  double  grad_norm;     /* max over the problems of |grad f_k|_inf at the returned point */
+  double  loss[PLIPMI_PROBE_MAX_K];  /* f_k at the returned point */
+} plipmi_probe_info;
+int plipmi_probe_fit(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int K, const float* pos_w, const float* neg_w,
+                     float alpha, int max_iter, float gtol, float* WB_inout, plipmi_probe_info* info_out, void* stream);
+int plipmi_probe_predict(plipmi_handle h, const float* X, int N, int D, const float* WB, int K, float* decision, int32_t* pred,
+                         void* stream);
 
 /* ---- measurement ------------------------------------------------------------
  * (kernel-level test entries and A/B hooks live in plipmi_test.h: same library, not part of the product interface) */

@@ -103,6 +103,11 @@ int plipmi_attention(int dtype, int impl, const void* qkv, void* out, int B, int
  * align_corners=False) in fp32.  src and dst are distinct device buffers. */
 int plipmi_resample_pos(const float* src, float* dst, int n0, int gh, int gw, int D, void* stream);
 
+/* One evaluation of the linear-probe objective (csrc/probe.hip; arguments as plipmi_probe_fit in plipmi.h) at WB [K, D + 1]:
+ * loss_out double [K] = f_k, grad_out fp32 [K, D + 1] = its gradient (weights, then intercept), both device buffers.  Enqueues only. */
+int plipmi_probe_loss_grad(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int K, const float* pos_w,
+                           const float* neg_w, float alpha, const float* WB, double* loss_out, float* grad_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,14 @@ class KernelStat(C.Structure):
                 ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+PROBE_MAX_K = 64     # include/plipmi.h PLIPMI_PROBE_MAX_K
+
+
+class ProbeInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("evaluations", C.c_int32), ("converged", C.c_int32), ("reserved", C.c_int32),
+                ("grad_norm", C.c_double), ("loss", C.c_double * PROBE_MAX_K)]
+
+
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 # kernel-level test entries and A/B hooks (include/plipmi_test.h): tests/, tools/ and bench.py's side fields only
 TEST_SYMBOLS = {
@@ -65,6 +73,7 @@ TEST_SYMBOLS = {
     "plipmi_attention": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "plipmi_qkv_attention": (_i, [_i, _vp, _vp, _vp, _vp, _i, _f, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "plipmi_resample_pos": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "plipmi_probe_loss_grad": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
 }
 # every symbol include/plipmi.h declares (the product interface): (restype, argtypes)
 SYMBOLS = {
@@ -91,6 +100,8 @@ SYMBOLS = {
     "plipmi_set_text_packing": (_i, [_vp, _i]),
     "plipmi_tower_shape": (_i, [_vp, _i, C.POINTER(C.c_int32)]),
     "plipmi_encode_tower_outputs": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "plipmi_probe_fit": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _f, _i, _f, _vp, C.POINTER(ProbeInfo), _vp]),
+    "plipmi_probe_predict": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "plipmi_profile_enable": (_i, [_vp, _i]),
     "plipmi_profile_read": (_i, [_vp, C.POINTER(KernelStat), _i, C.POINTER(_i)]),
 }
@@ -134,6 +145,7 @@ class PlipmiError(RuntimeError):
 
 
 ERR_TOKEN_ID = 5     # include/plipmi.h PLIPMI_ERR_TOKEN_ID
+ERR_NOT_CONVERGED = 6   # include/plipmi.h PLIPMI_ERR_NOT_CONVERGED (plipmi_probe_fit; Engine.probe_fit reports it in its info)
 
 
 def check(rc: int, what: str) -> None:

@@ -26,6 +26,7 @@
 #include "../../include/plipmi_test.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "probe_solver.h"
 
 #ifndef PLIPMI_DEFAULT_ATTENTION
 #define PLIPMI_DEFAULT_ATTENTION 1
@@ -197,6 +198,12 @@ struct plipmi_engine {
   // plipmi_similarity_topk scratch (allocated on first use, grown on demand)
   char* sim_ws = nullptr;
   size_t sim_ws_bytes = 0;
+  // linear-probe scratch (plipmi_probe_fit / _predict / _loss_grad): device partials + results, and a pinned host mirror of the
+  // trial point, gradient and losses.  Allocations of their own, grown on demand: never part of the tower workspace.
+  char* probe_ws = nullptr;
+  size_t probe_ws_bytes = 0;
+  char* probe_host = nullptr;
+  size_t probe_host_bytes = 0;
   // profiling
   bool prof = false;
   std::vector<ProfRec> recs;
@@ -943,6 +950,8 @@ void plipmi_destroy(plipmi_handle h) {
   for (auto& kv : h->graphs) if (kv.second.exec) hipGraphExecDestroy(kv.second.exec);
   if (h->cap_stream) hipStreamDestroy(h->cap_stream);
   if (h->sim_ws) hipFree(h->sim_ws);
+  if (h->probe_ws) hipFree(h->probe_ws);
+  if (h->probe_host) hipHostFree(h->probe_host);
   if (h->bad_id) hipHostFree(h->bad_id);
   delete h;
 }
@@ -1256,6 +1265,122 @@ int plipmi_similarity_topk(plipmi_handle h, const float* keys, int Nq, const flo
     }
     HIP_TRY(launch_topk_finish(ix, (size_t)rows * k, s));
   }
+  return PLIPMI_OK;
+}
+
+// ---- linear-probe head (probe.hip, probe_solver.h) ----------------------------------------------------------------------
+static int probe_check(plipmi_handle h, const void* X, int N, int D, const void* WB, int K) {
+  if (!h || !X || !WB) return fail(PLIPMI_ERR_INVALID, "null handle / X / WB");
+  if (N <= 0) return fail(PLIPMI_ERR_INVALID, "need N > 0 rows, got %d", N);
+  if (K < 1 || K > PLIPMI_PROBE_MAX_K) return fail(PLIPMI_ERR_INVALID, "need 1 <= K <= %d problems, got %d", PLIPMI_PROBE_MAX_K, K);
+  if (D < 4 || D > 1024 || D % 4) return fail(PLIPMI_ERR_INVALID, "embedding width %d unsupported (D %% 4 == 0, 4 <= D <= 1024)", D);
+  if (reinterpret_cast<uintptr_t>(X) % 16) return fail(PLIPMI_ERR_INVALID, "X must be 16-byte aligned");
+  return PLIPMI_OK;
+}
+static int probe_check_fit(const void* y, const void* pos_w, const void* neg_w, float alpha) {
+  if (!y || !pos_w || !neg_w) return fail(PLIPMI_ERR_INVALID, "null y / pos_w / neg_w");
+  if (!std::isfinite(alpha) || alpha <= 0.f) return fail(PLIPMI_ERR_INVALID, "alpha must be finite and > 0, got %g", (double)alpha);
+  return PLIPMI_OK;
+}
+static int probe_scratch(plipmi_handle h, int N, int D, int K, hipStream_t s) {
+  size_t go, lo, po;
+  const size_t need = probe_scratch_bytes(N, D, K, &go, &lo, &po);
+  if (need > h->probe_ws_bytes) {
+    if (h->probe_ws) { HIP_TRY(hipStreamSynchronize(s)); HIP_TRY(hipFree(h->probe_ws)); h->probe_ws = nullptr; h->probe_ws_bytes = 0; }
+    hipError_t me = hipMalloc(reinterpret_cast<void**>(&h->probe_ws), need);
+    if (me != hipSuccess) { h->probe_ws = nullptr; return fail(PLIPMI_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", need, hipGetErrorString(me)); }
+    h->probe_ws_bytes = need;
+  }
+  return PLIPMI_OK;
+}
+static int probe_eval(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int K, const float* pos_w, const float* neg_w,
+                      float alpha, const float* WB, float** grad, double** loss, hipStream_t s) {
+  Scope sc(h, s, "probe_loss_grad", 4.0 * N * (double)D * 16 * ((K + 15) / 16), (double)N * D * 4 * ((K + 15) / 16));
+  HIP_TRY(launch_probe_loss_grad(X, N, D, y, WB, K, pos_w, neg_w, K == 1 ? 1 : 0, alpha, h->probe_ws, grad, loss, s));
+  return PLIPMI_OK;
+}
+
+int plipmi_probe_loss_grad(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int K, const float* pos_w,
+                           const float* neg_w, float alpha, const float* WB, double* loss_out, float* grad_out, void* stream) {
+  RUN(probe_check(h, X, N, D, WB, K));
+  RUN(probe_check_fit(y, pos_w, neg_w, alpha));
+  if (!loss_out || !grad_out) return fail(PLIPMI_ERR_INVALID, "null loss_out / grad_out");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  RUN(probe_scratch(h, N, D, K, s));
+  float* grad; double* loss;
+  RUN(probe_eval(h, X, N, D, y, K, pos_w, neg_w, alpha, WB, &grad, &loss, s));
+  HIP_TRY(hipMemcpyAsync(grad_out, grad, (size_t)K * (D + 1) * 4, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(loss_out, loss, (size_t)K * 8, hipMemcpyDeviceToDevice, s));
+  return PLIPMI_OK;
+}
+
+int plipmi_probe_fit(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int K, const float* pos_w, const float* neg_w,
+                     float alpha, int max_iter, float gtol, float* WB_inout, plipmi_probe_info* info_out, void* stream) {
+  RUN(probe_check(h, X, N, D, WB_inout, K));
+  RUN(probe_check_fit(y, pos_w, neg_w, alpha));
+  if (max_iter < 1 || !std::isfinite(gtol) || gtol <= 0.f) return fail(PLIPMI_ERR_INVALID, "need max_iter >= 1 and a finite gtol > 0");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  RUN(probe_scratch(h, N, D, K, s));
+  const int n = D + 1;
+  const size_t wb_bytes = (size_t)K * n * 4, host_need = 2 * align_up(wb_bytes, 256) + align_up((size_t)K * 8, 256);
+  if (host_need > h->probe_host_bytes) {
+    if (h->probe_host) { HIP_TRY(hipStreamSynchronize(s)); HIP_TRY(hipHostFree(h->probe_host)); h->probe_host = nullptr; h->probe_host_bytes = 0; }
+    hipError_t me = hipHostMalloc(reinterpret_cast<void**>(&h->probe_host), host_need, hipHostMallocDefault);
+    if (me != hipSuccess) { h->probe_host = nullptr; return fail(PLIPMI_ERR_NOMEM, "hipHostMalloc(%zu bytes) failed: %s", host_need, hipGetErrorString(me)); }
+    h->probe_host_bytes = host_need;
+  }
+  float* wb_h = reinterpret_cast<float*>(h->probe_host);
+  float* g_h = reinterpret_cast<float*>(h->probe_host + align_up(wb_bytes, 256));
+  double* l_h = reinterpret_cast<double*>(h->probe_host + 2 * align_up(wb_bytes, 256));
+
+  HIP_TRY(hipMemcpyAsync(wb_h, WB_inout, wb_bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (size_t i = 0; i < (size_t)K * n; ++i)
+    if (!std::isfinite(wb_h[i])) return fail(PLIPMI_ERR_INVALID, "the starting point WB_inout holds a non-finite value");
+  std::vector<ProbeLbfgs> prob(K);
+  for (int k = 0; k < K; ++k) prob[k].init(wb_h + (size_t)k * n, n, max_iter, (double)gtol);
+  int evals = 0;
+  // every pass evaluates the K current trial points; the trial point travels through WB_inout itself
+  for (;;) {
+    for (int k = 0; k < K; ++k) prob[k].trial(wb_h + (size_t)k * n);
+    HIP_TRY(hipMemcpyAsync(WB_inout, wb_h, wb_bytes, hipMemcpyHostToDevice, s));
+    bool all_done = true;
+    for (int k = 0; k < K; ++k) all_done = all_done && prob[k].done;
+    if (all_done) break;           // WB_inout now holds every problem's final point
+    float* grad; double* loss;
+    RUN(probe_eval(h, X, N, D, y, K, pos_w, neg_w, alpha, WB_inout, &grad, &loss, s));
+    HIP_TRY(hipMemcpyAsync(g_h, grad, wb_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(l_h, loss, (size_t)K * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ++evals;
+    for (int k = 0; k < K; ++k) prob[k].feed(l_h[k], g_h + (size_t)k * n);
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  int iters = 0, conv = 0, worst = -1;
+  double gmax = 0;
+  for (int k = 0; k < K; ++k) {
+    iters = std::max(iters, prob[k].iters);
+    conv += prob[k].converged ? 1 : 0;
+    if (prob[k].gnorm >= gmax) { gmax = prob[k].gnorm; worst = k; }
+  }
+  if (info_out) {
+    memset(info_out, 0, sizeof(*info_out));
+    info_out->iterations = iters; info_out->evaluations = evals; info_out->converged = conv; info_out->grad_norm = gmax;
+    for (int k = 0; k < K; ++k) info_out->loss[k] = prob[k].f;
+  }
+  if (conv != K)
+    return fail(PLIPMI_ERR_NOT_CONVERGED, "probe fit: %d of %d problems did not reach |grad|_inf <= %g within %d iterations "
+                "(largest %g, problem %d, %d evaluations); WB holds the best point found", K - conv, K, (double)gtol, max_iter, gmax, worst, evals);
+  return PLIPMI_OK;
+}
+
+int plipmi_probe_predict(plipmi_handle h, const float* X, int N, int D, const float* WB, int K, float* decision, int32_t* pred,
+                         void* stream) {
+  RUN(probe_check(h, X, N, D, WB, K));
+  if (!pred) return fail(PLIPMI_ERR_INVALID, "null pred");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Scope sc(h, s, "probe_predict", 2.0 * N * (double)D * K, (double)N * D * 4);
+  HIP_TRY(launch_probe_predict(X, N, D, WB, K, decision, pred, s));
   return PLIPMI_OK;
 }
 

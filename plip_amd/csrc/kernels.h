@@ -119,6 +119,17 @@ hipError_t launch_attention(const void* qkv, void* out, int dtype, int B, int S,
 hipError_t launch_attention_probs(const void* qkv, float* probs, int dtype, int B, int S, int H, int causal, const int64_t* key_mask,
                                   hipStream_t s);
 
+// Linear-probe head (probe.hip): one loss-and-gradient evaluation of the K one-vs-rest logistic problems at WB [K, D + 1] (weights,
+// then intercept) over X [N, D] fp32 with int32 labels y: problem k's positive label is class_base + k, its sample weights pos_w[k] /
+// neg_w[k].  `scratch` (probe_scratch_bytes) holds the per-workgroup partials and the results: *grad = fp32 [K, D + 1], *loss =
+// double [K] point into it.  D % 4 == 0, D <= 1024, K <= 64, X 16-byte aligned.  Deterministic: fixed-order reductions.
+size_t probe_scratch_bytes(int N, int D, int K, size_t* grad_off, size_t* loss_off, size_t* partl_off);
+hipError_t launch_probe_loss_grad(const float* X, int N, int D, const int32_t* y, const float* WB, int K, const float* pos_w,
+                                  const float* neg_w, int class_base, float alpha, char* scratch, float** grad, double** loss,
+                                  hipStream_t s);
+// decision [N, K] = X W^T + b (may be nullptr) and pred [N] = first arg-max over the K problems (K == 1: z > 0)
+hipError_t launch_probe_predict(const float* X, int N, int D, const float* WB, int K, float* decision, int32_t* pred, hipStream_t s);
+
 // The text tower's LayerNorm-folded q/k/v projection with the attention in its epilogue (qkv_attention.hip): one launch, no
 // `qkv` tensor in memory.  A = the residual stream's operand plane [B*S, D], W / c2 = the folded q | k | v weights [3D, D] and
 // biases, stats = the rows' LayerNorm partials [B*S, D/64, 2]; out = attention output [B*S, D], bit-identical to

@@ -1,0 +1,406 @@
+// probe.hip -- the linear-probe head (reference: reproducibility/evaluation/linear_probing/linear_classifier.py, scikit-learn's
+// SGDClassifier(loss="log_loss", penalty="l2", class_weight="balanced")): one fused loss-and-gradient pass over cached
+// embeddings for all K one-vs-rest problems at once, and the predict kernel.  The solver that calls it is on the host
+// (engine.hip plipmi_probe_fit).
+//
+//   f_k(w, b) = (1/N) sum_i c_ik log(1 + exp(-t_ik (x_i.w + b))) + alpha/2 |w|^2      t_ik = +1 if y_i == k else -1
+//
+// probe_loss_grad_kernel<CT>: persistent workgroups of four waves walk 32-row tiles of X [N, D] fp32.  A tile is fetched from HBM
+// ONCE, as 16-byte loads into registers while the previous tile is being computed, and stored to LDS ([32][Dp], Dp = D rounded up
+// to 64 = 64 CT floats); both products read it from there:
+//   phase 1  Z[32, 16] = X_tile W^T    v_mfma_f32_16x16x4_f32 (exact fp32), A = X rows (k = d), B = W; D is split over the four
+//            waves (their W fragments stay in registers for the whole kernel), the four partial Z tiles meet in LDS;
+//   residual one (row, class) pair per thread and half tile: z = b + the four partials in wave order, stable
+//            log1p(exp(-|z|)) + max(-t z, 0), r = c (sigmoid(z) - [y == k]) into LDS; loss and intercept-gradient sums stay in
+//            the thread, in double, for the whole kernel;
+//   phase 2  G[16, D] += R^T X_tile    the same instruction, A = R^T (k = row), B = X; a wave owns CT 16-column tiles of G, whose
+//            accumulators live in registers for the whole kernel.
+// The LDS image of X is XOR-swizzled (column ^ probe_swz(row)) so that phase 1 (16 rows x 4 consecutive columns per wave
+// read) and phase 2 (4 rows x 16 consecutive columns) are both free of bank conflicts; a 16-byte store stays contiguous.
+// Every workgroup writes its partial G, g_b and loss to its own slot; probe_finish_kernel sums the slots in a FIXED order in
+// double (no floating-point atomics: the same inputs give the same bits), divides by N and adds the penalty's terms.
+// More than 16 problems run as ceil(K / 16) groups on grid.y, each group a pass over X of its own.
+//
+// probe_predict_kernel<CT>: the same tile and phase 1 for every group of 16 classes; writes the decision values [N, K] (optional)
+// and the first arg-max per row (one problem: z > 0), so only [N] int32 come back to the host.
+//
+// A label outside [0, C) matches no problem: the row counts as a negative everywhere; y never indexes anything.
+#include <algorithm>
+#include <type_traits>
+
+#include "kernels.h"
+
+namespace plipmi {
+
+namespace {
+
+constexpr int kRows = 32;        // rows of X per tile
+constexpr int kThreads = 256;    // four waves
+constexpr int kGroup = 16;       // problems per MFMA tile
+
+__device__ __forceinline__ int probe_swz(int row) { return ((row & 3) << 4) | (((row >> 2) & 3) << 2); }
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+template <int CT> struct ProbeTile {
+  static constexpr int Dp = 64 * CT;          // LDS row length (floats)
+  static constexpr int NV = 2 * CT;           // 16-byte loads per thread and tile
+  static constexpr int KS = 4 * CT;           // phase-1 k steps (of 4 columns) per wave
+  float4 pre[NV];
+
+  // rows [row0, row0 + 32) of X -> registers (zeros past N and past D)
+  __device__ __forceinline__ void fetch(const float* __restrict__ X, int N, int D, long row0, int tid) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int i = tid + kThreads * j, r = i / (Dp / 4), d = (i - r * (Dp / 4)) * 4;
+      const long gr = row0 + r;
+      pre[j] = (gr < N && d < D) ? *reinterpret_cast<const float4*>(X + gr * D + d) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  __device__ __forceinline__ void stage(float* xs, int tid) const {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int i = tid + kThreads * j, r = i / (Dp / 4), d = (i - r * (Dp / 4)) * 4;
+      *reinterpret_cast<float4*>(&xs[r * Dp + (d ^ probe_swz(r))]) = pre[j];
+    }
+  }
+  // the same without the stop in registers (wide rows, where the registers go to the accumulators; the predict kernel)
+  __device__ __forceinline__ static void direct(const float* __restrict__ X, int N, int D, long row0, int tid, float* xs) {
+#pragma unroll 4
+    for (int j = 0; j < NV; ++j) {
+      const int i = tid + kThreads * j, r = i / (Dp / 4), d = (i - r * (Dp / 4)) * 4;
+      const long gr = row0 + r;
+      *reinterpret_cast<float4*>(&xs[r * Dp + (d ^ probe_swz(r))]) =
+          (gr < N && d < D) ? *reinterpret_cast<const float4*>(X + gr * D + d) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  // this wave's slice of W for problems kbase .. kbase + 15: wf[s] = W[kbase + (lane & 15)][4 (wave KS + s) + (lane >> 4)]
+  __device__ __forceinline__ static void load_w(float (&wf)[KS], const float* __restrict__ WB, int K, int D, int kbase, int wave, int lane) {
+    const int cls = kbase + (lane & 15);
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const int d = (wave * KS + s) * 4 + (lane >> 4);
+      wf[s] = (cls < K && d < D) ? WB[(size_t)cls * (D + 1) + d] : 0.f;
+    }
+  }
+  // phase 1: this wave's partial Z for the tile's two 16-row blocks -> zp[wave][32][16]
+  __device__ __forceinline__ static void scores(const float* xs, const float (&wf)[KS], float* zp, int wave, int lane) {
+    f32x4 z0 = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
+    const int m = lane & 15, k = lane >> 4, sw = probe_swz(m);      // probe_swz(m + 16) == probe_swz(m)
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const int d = ((wave * KS + s) * 4 + k) ^ sw;
+      z0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xs[m * Dp + d], wf[s], z0, 0, 0, 0);
+      z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xs[(m + 16) * Dp + d], wf[s], z1, 0, 0, 0);
+    }
+    float* o = zp + wave * (kRows * kGroup);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {      // C/D layout: column (problem) = lane & 15, row = 4 (lane >> 4) + j
+      o[(4 * k + j) * kGroup + m] = z0[j];
+      o[(16 + 4 * k + j) * kGroup + m] = z1[j];
+    }
+  }
+};
+
+template <int CT>
+__global__ __launch_bounds__(kThreads) void probe_loss_grad_kernel(const float* __restrict__ X, int N, int D, const int32_t* __restrict__ y,
+                                                                   const float* __restrict__ WB, int K, const float* __restrict__ pos_w,
+                                                                   const float* __restrict__ neg_w, int class_base,
+                                                                   float* __restrict__ part_g, double* __restrict__ part_l) {
+  using T = ProbeTile<CT>;
+  constexpr int Dp = T::Dp;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* xs = lds;                                   // [32][Dp], swizzled
+  float* zp = xs + kRows * Dp;                       // [4][32][16] partial scores; at the end: the loss / g_b reduction
+  float* rs = zp + 4 * kRows * kGroup;               // [32][16] residuals
+
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int kbase = blockIdx.y * kGroup, KP = gridDim.y * kGroup;
+  const long ntiles = ((long)N + kRows - 1) / kRows;
+
+  float wf[T::KS];
+  T::load_w(wf, WB, K, D, kbase, wave, lane);
+  f32x4 g[CT];
+#pragma unroll
+  for (int j = 0; j < CT; ++j) g[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // residual stage: this thread's problem and its two rows of a tile
+  const int rc = tid & 15, rr = tid >> 4, cls = kbase + rc;
+  const bool live = cls < K;
+  const float bias = live ? WB[(size_t)cls * (D + 1) + D] : 0.f;
+  const float pw = live ? pos_w[cls] : 0.f, nw = live ? neg_w[cls] : 0.f;
+  const int target = class_base + cls;               // the label that is positive for this problem
+  double loss = 0.0, gb = 0.0;
+
+  // D <= 512: the next tile waits in registers while this one is computed; wider rows need those registers for wf and g
+  constexpr bool kPrefetch = CT <= 8;
+  T tile;
+  long t = blockIdx.x;
+  int ynext[2] = {-1, -1};
+  auto fetch = [&](long tl) {
+    if constexpr (kPrefetch) tile.fetch(X, N, D, tl * kRows, tid);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) { const long gr = tl * kRows + rr + 16 * h; ynext[h] = gr < N ? y[gr] : -1; }
+  };
+  if (t < ntiles) fetch(t);
+  while (t < ntiles) {
+    if constexpr (kPrefetch) tile.stage(xs, tid); else T::direct(X, N, D, t * kRows, tid, xs);
+    const int ycur[2] = {ynext[0], ynext[1]};
+    __syncthreads();
+    const long next = t + gridDim.x;
+    if (next < ntiles) fetch(next);     // in flight under this tile's arithmetic
+    T::scores(xs, wf, zp, wave, lane);
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int r = rr + 16 * h;
+      const long gr = t * kRows + r;
+      float res = 0.f;
+      if (live && gr < N) {
+        const int o = r * kGroup + rc;
+        const float z = bias + (((zp[o] + zp[kRows * kGroup + o]) + zp[2 * kRows * kGroup + o]) + zp[3 * kRows * kGroup + o]);
+        const bool pos = ycur[h] == target;
+        const float c = pos ? pw : nw;
+        const float e = expf(-fabsf(z));
+        const float sig = z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+        const float tz = pos ? z : -z;
+        loss += (double)(c * (log1pf(e) + fmaxf(-tz, 0.f)));
+        res = c * (sig - (pos ? 1.f : 0.f));
+        gb += (double)res;
+      }
+      rs[r * kGroup + rc] = res;
+    }
+    __syncthreads();
+    // phase 2: G[problem][d] += sum_row R[row][problem] X[row][d]
+    {
+      const int m = lane & 15, k = lane >> 4;
+#pragma unroll
+      for (int q = 0; q < kRows / 4; ++q) {
+        const int row = 4 * q + k;
+        const float a = rs[row * kGroup + m];
+        const float* xr = xs + row * Dp;
+        const int sw = probe_swz(row);
+#pragma unroll
+        for (int j = 0; j < CT; ++j) g[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xr[((wave * CT + j) * 16 + m) ^ sw], g[j], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+    t = next;
+  }
+
+  // this workgroup's slot: part_g [gridDim.x][KP][D + 1], part_l [gridDim.x][KP]
+  float* pg = part_g + ((size_t)blockIdx.x * KP + kbase) * (D + 1);
+  {
+    const int m = lane & 15, k = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < CT; ++j) {
+      const int d = (wave * CT + j) * 16 + m;
+      if (d < D) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pg[(size_t)(4 * k + i) * (D + 1) + d] = g[j][i];     // C/D: row (problem) = 4 (lane >> 4) + i
+      }
+    }
+  }
+  double* red = reinterpret_cast<double*>(zp);        // [2][16 row slots][16 problems] doubles = 4 KiB of zp's 8 KiB
+  red[rr * kGroup + rc] = loss;
+  red[256 + rr * kGroup + rc] = gb;
+  __syncthreads();
+  if (tid < kGroup) {
+    double l = 0.0, b = 0.0;
+    for (int i = 0; i < 16; ++i) { l += red[i * kGroup + tid]; b += red[256 + i * kGroup + tid]; }
+    pg[(size_t)tid * (D + 1) + D] = (float)b;
+    part_l[(size_t)blockIdx.x * KP + kbase + tid] = l;
+  }
+}
+
+// grad[k][d] = (sum over workgroups, in order)/N + alpha W[k][d]; the intercept's has no penalty;
+// loss[k] = (sum)/N + alpha/2 |w_k|^2.  grid (K, ceil((D + 1) / 64)), 256 threads = 64 columns x 4 slices of the workgroups.
+__global__ __launch_bounds__(256) void probe_finish_kernel(const float* __restrict__ part_g, const double* __restrict__ part_l, int nwg,
+                                                          int KP, const float* __restrict__ WB, int N, int D, float alpha,
+                                                          float* __restrict__ grad, double* __restrict__ loss) {
+  __shared__ double sh[4][64];
+  const int k = blockIdx.x, tid = threadIdx.x, c = tid & 63, q = tid >> 6;
+  const int d = blockIdx.y * 64 + c;
+  double acc = 0.0;
+  if (d <= D) {
+    const int w0 = (int)((long)nwg * q / 4), w1 = (int)((long)nwg * (q + 1) / 4);
+    for (int w = w0; w < w1; ++w) acc += (double)part_g[((size_t)w * KP + k) * (D + 1) + d];
+  }
+  sh[q][c] = acc;
+  __syncthreads();
+  if (q == 0 && d <= D) {
+    const double s = ((sh[0][c] + sh[1][c]) + sh[2][c]) + sh[3][c];
+    const double pen = d < D ? (double)alpha * (double)WB[(size_t)k * (D + 1) + d] : 0.0;
+    grad[(size_t)k * (D + 1) + d] = (float)(s / N + pen);
+  }
+  if (blockIdx.y == 0 && q == 1) {       // one wave: the loss of problem k
+    double l = 0.0, w2 = 0.0;
+    for (int w = c; w < nwg; w += 64) l += part_l[(size_t)w * KP + k];
+    for (int i = c; i < D; i += 64) { const double v = WB[(size_t)k * (D + 1) + i]; w2 += v * v; }
+    l = wave_sum_f64(l);
+    w2 = wave_sum_f64(w2);
+    if (c == 0) loss[k] = l / N + 0.5 * (double)alpha * w2;
+  }
+}
+
+template <int CT>
+__global__ __launch_bounds__(kThreads) void probe_predict_kernel(const float* __restrict__ X, int N, int D, const float* __restrict__ WB,
+                                                                 int K, float* __restrict__ decision, int32_t* __restrict__ pred) {
+  using T = ProbeTile<CT>;
+  constexpr int Dp = T::Dp;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* xs = lds;
+  float* zp = xs + kRows * Dp;                       // [4][32][16]
+  float* best = zp + 4 * kRows * kGroup;             // [32][16] running (value, index) candidates: best[r][c], arg below
+  int* arg = reinterpret_cast<int*>(best + kRows * kGroup);
+
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int rc = tid & 15, rr = tid >> 4;
+  const long ntiles = ((long)N + kRows - 1) / kRows;
+  const int groups = (K + kGroup - 1) / kGroup;
+  for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    T::direct(X, N, D, t * kRows, tid, xs);
+    __syncthreads();
+    for (int gI = 0; gI < groups; ++gI) {
+      const int kbase = gI * kGroup, cls = kbase + rc;
+      float wf[T::KS];
+      T::load_w(wf, WB, K, D, kbase, wave, lane);
+      T::scores(xs, wf, zp, wave, lane);
+      __syncthreads();
+      const float bias = cls < K ? WB[(size_t)cls * (D + 1) + D] : 0.f;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int r = rr + 16 * h, o = r * kGroup + rc;
+        const long gr = t * kRows + r;
+        const float z = bias + (((zp[o] + zp[kRows * kGroup + o]) + zp[2 * kRows * kGroup + o]) + zp[3 * kRows * kGroup + o]);
+        if (cls < K && gr < N && decision) decision[gr * K + cls] = z;
+        // column rc of the row keeps the first maximum over the problems rc, rc + 16, ... (ascending: ties keep the earlier)
+        if (cls < K && (gI == 0 || z > best[o])) { best[o] = z; arg[o] = cls; }
+      }
+      __syncthreads();
+    }
+    if (tid < kRows) {
+      const long gr = t * kRows + tid;
+      if (gr < N) {
+        if (K == 1) {
+          pred[gr] = best[tid * kGroup] > 0.f ? 1 : 0;
+        } else {
+          float bv = best[tid * kGroup];
+          int bi = arg[tid * kGroup];
+          const int cols = K < kGroup ? K : kGroup;
+          for (int c = 1; c < cols; ++c) {
+            const float v = best[tid * kGroup + c];
+            const int i = arg[tid * kGroup + c];
+            if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+          }
+          pred[gr] = bi;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+size_t lds_fit(int CT) { return ((size_t)kRows * 64 * CT + 4 * kRows * kGroup + kRows * kGroup) * 4; }
+size_t lds_predict(int CT) { return ((size_t)kRows * 64 * CT + 4 * kRows * kGroup + 2 * kRows * kGroup) * 4; }
+
+int compute_units() {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0;
+    hipDeviceProp_t p;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
+    if (cus <= 0) cus = 256;
+  }
+  return cus;
+}
+
+}  // namespace
+
+// 64-column blocks of the LDS row, rounded up to an instantiated tile (PROBE_DISPATCH)
+int probe_col_tiles(int D) {
+  const int ct = (D + 63) / 64;
+  return ct <= 2 ? ct : ct <= 4 ? 4 : ct <= 6 ? 6 : ct <= 8 ? 8 : ct <= 12 ? 12 : 16;
+}
+
+// workgroups along x for N rows at width D: one per tile, at most one per CU (the kernel's registers -- next tile, W slice, G
+// accumulators -- allow one workgroup per CU; its own prefetch is what overlaps the loads with the arithmetic)
+int probe_workgroups(int N, int D) {
+  const long ntiles = ((long)N + kRows - 1) / kRows;
+  return (int)std::max<long>(1, std::min<long>(ntiles, compute_units()));
+}
+
+size_t probe_scratch_bytes(int N, int D, int K, size_t* grad_off, size_t* loss_off, size_t* partl_off) {
+  const size_t KP = (size_t)((K + kGroup - 1) / kGroup) * kGroup, nwg = probe_workgroups(N, D);
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  size_t off = up(nwg * KP * (D + 1) * 4);
+  *partl_off = off; off += up(nwg * KP * 8);
+  *grad_off = off;  off += up((size_t)K * (D + 1) * 4);
+  *loss_off = off;  off += up((size_t)K * 8);
+  return off;
+}
+
+// run f(std::integral_constant<int, CT>) for the instantiated tile that probe_col_tiles chose
+template <typename F> hipError_t probe_dispatch(int ct, F&& f) {
+  switch (ct) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 6: return f(std::integral_constant<int, 6>());
+    case 8: return f(std::integral_constant<int, 8>());
+    case 12: return f(std::integral_constant<int, 12>());
+    default: return f(std::integral_constant<int, 16>());
+  }
+}
+
+hipError_t launch_probe_loss_grad(const float* X, int N, int D, const int32_t* y, const float* WB, int K, const float* pos_w,
+                                  const float* neg_w, int class_base, float alpha, char* scratch, float** grad, double** loss,
+                                  hipStream_t s) {
+  size_t go, lo, po;
+  probe_scratch_bytes(N, D, K, &go, &lo, &po);
+  float* part_g = reinterpret_cast<float*>(scratch);
+  double* part_l = reinterpret_cast<double*>(scratch + po);
+  *grad = reinterpret_cast<float*>(scratch + go);
+  *loss = reinterpret_cast<double*>(scratch + lo);
+  const int groups = (K + kGroup - 1) / kGroup, nwg = probe_workgroups(N, D);
+  hipError_t e = probe_dispatch(probe_col_tiles(D), [&](auto ct) -> hipError_t {
+    constexpr int CT = decltype(ct)::value;
+    const size_t lds = lds_fit(CT);
+    static bool attr_done = false;
+    if (!attr_done) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&probe_loss_grad_kernel<CT>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      attr_done = true;
+    }
+    probe_loss_grad_kernel<CT><<<dim3(nwg, groups), kThreads, lds, s>>>(X, N, D, y, WB, K, pos_w, neg_w, class_base, part_g, part_l);
+    return hipGetLastError();
+  });
+  if (e != hipSuccess) return e;
+  probe_finish_kernel<<<dim3(K, (D + 1 + 63) / 64), 256, 0, s>>>(part_g, part_l, nwg, groups * kGroup, WB, N, D, alpha, *grad, *loss);
+  return hipGetLastError();
+}
+
+hipError_t launch_probe_predict(const float* X, int N, int D, const float* WB, int K, float* decision, int32_t* pred, hipStream_t s) {
+  const long ntiles = ((long)N + kRows - 1) / kRows;
+  return probe_dispatch(probe_col_tiles(D), [&](auto ct) -> hipError_t {
+    constexpr int CT = decltype(ct)::value;
+    const size_t lds = lds_predict(CT);
+    static bool attr_done = false;
+    if (!attr_done) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&probe_predict_kernel<CT>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      attr_done = true;
+    }
+    const int nwg = (int)std::max<long>(1, std::min<long>(ntiles, (long)compute_units() * 4));
+    probe_predict_kernel<CT><<<nwg, kThreads, lds, s>>>(X, N, D, WB, K, decision, pred);
+    return hipGetLastError();
+  });
+}
+
+}  // namespace plipmi

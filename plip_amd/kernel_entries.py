@@ -216,3 +216,21 @@ def resample_pos(table: torch.Tensor, gh: int, gw: int) -> torch.Tensor:
         _lib.check(lib.plipmi_resample_pos(_ptr(table), _ptr(out), n0, int(gh), int(gw), table.shape[1],
                                            C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)), "plipmi_resample_pos")
     return out
+
+
+def probe_loss_grad(engine, x: torch.Tensor, y: torch.Tensor, wb: torch.Tensor, pos_w: torch.Tensor, neg_w: torch.Tensor, alpha: float):
+    """One evaluation of the linear-probe objective (include/plipmi_test.h ``plipmi_probe_loss_grad``): x fp32 [N, D], y int32 [N],
+    wb fp32 [K, D + 1], pos_w / neg_w fp32 [K], all on the engine's device -> (loss double [K], grad fp32 [K, D + 1])."""
+    lib = _lib.load()
+    for t, dt in ((x, torch.float32), (y, torch.int32), (wb, torch.float32), (pos_w, torch.float32), (neg_w, torch.float32)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous()
+    N, D = x.shape
+    K = wb.shape[0]
+    assert wb.shape[1] == D + 1 and y.shape == (N,) and pos_w.shape == (K,) and neg_w.shape == (K,)
+    loss = torch.empty((K,), dtype=torch.float64, device=x.device)
+    grad = torch.empty((K, D + 1), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.plipmi_probe_loss_grad(engine._h, _ptr(x), N, D, _ptr(y), K, _ptr(pos_w), _ptr(neg_w), float(alpha), _ptr(wb),
+                                              _ptr(loss), _ptr(grad), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
+                   "plipmi_probe_loss_grad")
+    return loss, grad

@@ -2,7 +2,8 @@
 
 ``retrieval_metrics`` (metrics.py:5-15): p@10 / p@50 = share of queries whose target index is among the
 first 10 / 50 retrieved indices.  ``eval_metrics`` (metrics.py:19-75): accuracy, support-weighted
-precision / recall / F1, multi-class Matthews correlation, AUC for a binary problem with scores, and the
+(``average_method="weighted"``, the default) or unweighted-mean (``"macro"``, what the linear probe asks for) precision / recall /
+F1 with sklearn's zero-division rule (0.0), multi-class Matthews correlation, AUC for a binary problem with scores, and the
 binary confusion counts the reference derives for integer labels 1 (positive) and 0 (negative).
 """
 from __future__ import annotations
@@ -46,8 +47,8 @@ def _binary_auc(y_true, score) -> float:
 
 def eval_metrics(y_true, y_pred, y_pred_proba=None, average_method: str = "weighted", verbose: bool = False):
     assert len(y_true) == len(y_pred)
-    if average_method != "weighted":
-        raise NotImplementedError("only the reference's default, support-weighted averaging, is provided")
+    if average_method not in ("weighted", "macro"):
+        raise NotImplementedError("averaging is 'weighted' (the reference's default) or 'macro' (its linear probe)")
     n = len(y_true)
     cm = _confusion(y_true, y_pred)
     tp_c = np.diag(cm).astype(np.float64)
@@ -57,7 +58,10 @@ def eval_metrics(y_true, y_pred, y_pred_proba=None, average_method: str = "weigh
         prec_c = np.where(predicted > 0, tp_c / predicted, 0.0)
         rec_c = np.where(support > 0, tp_c / support, 0.0)
         f1_c = np.where(prec_c + rec_c > 0, 2 * prec_c * rec_c / (prec_c + rec_c), 0.0)
-    w = support / max(n, 1)
+    if average_method == "macro":                        # sklearn averages over the labels present in y_true OR y_pred: all of cm's
+        w = np.full(len(tp_c), 1.0 / max(len(tp_c), 1))
+    else:
+        w = support / max(n, 1)
     acc = float(tp_c.sum() / n) if n else float("nan")
     # multi-class MCC (Gorodkin's R_K): (c s - sum p_k t_k) / sqrt((s^2 - sum p_k^2)(s^2 - sum t_k^2))
     c, s = tp_c.sum(), float(n)
