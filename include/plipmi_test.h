@@ -66,7 +66,7 @@ int plipmi_gemm_nt_traced(int dtype, int epilogue, int variant, int M, int N, in
 
 /* Kernel-level entry for the LayerNorm-folded epilogues of the 16-bit engines (gemm.h EPI_BIAS_LN / EPI_QGELU_LN /
  * EPI_RESID_EMIT / EPI_RESID_SPLIT; dtype PLIPMI_BF16 | PLIPMI_F16, A, W as raw uint16; "h16" below = that type):
- *   mode 0: C(h16) = rstd[m] * A.W^T + bias[n]       rstd from `stats` [M, ns, 2] fp32 = per-64-column partials
+ *   mode 0: C(h16) = rstd[m] * A.W^T + bias[n]       rstd from `stats` [M, ns, 2] fp32 = per-64-column partials (ns even)
  *   mode 1: C(h16) = quickgelu(that)                 {sum, centred M2} of the LayerNorm input rows (D = 64 * ns), eps as
  *                                                     given; W is expected to carry LayerNorm's gain with CENTRED rows
  *                                                     (sum_k W[n,k] = 0), which is what subtracts the row mean
@@ -107,6 +107,45 @@ int plipmi_resample_pos(const float* src, float* dst, int n0, int gh, int gw, in
  * loss_out double [K] = f_k, grad_out fp32 [K, D + 1] = its gradient (weights, then intercept), both device buffers.  Enqueues only. */
 int plipmi_probe_loss_grad(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int K, const float* pos_w,
                            const float* neg_w, float alpha, const float* WB, double* loss_out, float* grad_out, void* stream);
+
+/* Kernel-level entries of the kernels AROUND the GEMMs (csrc/kernels.hip, csrc/attention_probs.hip), for tests/test_gpu_small_kernels.py:
+ * each checks its arguments on the host (PLIPMI_ERR_INVALID before any launch), runs the engine's own launcher on `stream` and returns.
+ * dtype / y_dtype are PLIPMI_F32 | PLIPMI_BF16 | PLIPMI_F16 (16-bit buffers as raw uint16); "planes" = the split residual form
+ * {hi uint16 [rows, D], lo = the blocked 8-bit remainder plane, ((rows + 15) / 16) * 16 * D bytes}; st = fp32 [rows, D / 64, 2]
+ * per-64-column partials {sum, centred M2}.  All pointers are device buffers; nothing here synchronises. */
+
+/* probs fp32 [B, H, S, S] = softmax(q k^T + causal + key mask) from qkv [B*S, 3*64*H] (scale folded into q), as HF's eager attention:
+ * masked entries exactly 0, a row with no live key all 0.  key_mask int64 [B, S] or NULL.  1 <= S <= 1024. */
+int plipmi_attention_probs(int dtype, const void* qkv, float* probs, int B, int S, int H, int causal, const int64_t* key_mask,
+                           void* stream);
+/* y [rows, D] (y_dtype, contiguous) = LayerNorm(x[r * x_row_stride : + D]) * g + b.  D % 4 == 0, D <= 2048, x_row_stride % 4 == 0 and
+ * >= D, x 16-byte aligned.  y may be x itself for fp32 rows of stride D. */
+int plipmi_layernorm(const float* x, size_t x_row_stride, const float* g, const float* b, void* y, int y_dtype, int rows, int D,
+                     float eps, void* stream);
+/* the same rows written as planes of `dtype` (16-bit) plus their statistics partials.  D % 64 == 0, D <= 2048. */
+int plipmi_layernorm_emit(int dtype, const float* x, const float* g, const float* b, void* hi, void* lo, float* st, int rows, int D,
+                          float eps, void* stream);
+/* the weight fold of the 16-bit engines: Wf [rows, K] (dtype) = pre * (W * g, rows centred), c2 [rows] = pre * (W . b + bias).  K % 4 == 0. */
+int plipmi_fold_ln(int dtype, const float* W, const float* bias, const float* g, const float* b, void* Wf, float* c2, int rows, int K,
+                   float pre, void* stream);
+/* token + position rows tok[ids[b, s]] + pos[s] as planes + statistics.  packed = 0: every row, [B*S, D] (eos_id, cu, rowmap, m unused).
+ * packed = 1: the pack plan first -- len[b] = EOS position + 1 (eos_id == 2 or < 0: first arg-max of the ids, else the first eos_id, 0
+ * if absent), cu int32 [B + 1] = exclusive prefix sums, rowmap int32 [B*S] = (b << 8) | s of each packed row, m int32 [1] = cu[B] --,
+ * then rows 0 .. m-1 only.  bad_id: NULL or an int32 flag raised by an id outside [0, vocab).  D % 64 == 0; packed: S <= 256. */
+int plipmi_text_embed_emit(int dtype, int packed, const int64_t* ids, const float* tok, const float* pos, void* hi, void* lo, float* st,
+                           int B, int S, int D, int vocab, int eos_id, int32_t* cu, int32_t* rowmap, int32_t* m, int32_t* bad_id,
+                           void* stream);
+/* the pooled row of x fp32 [B, S, D] (ids == NULL: row 0, else the caption's EOS row by the rule above) through LayerNorm and
+ *   mode 0: the projection Wt [D, P] (transposed weights), optionally L2-normalised -> out [B, P]   (D <= 2048, P <= 1024)
+ *   mode 1: nothing more -> out [B, D]                                                               (D % 4 == 0, D <= 2048) */
+int plipmi_pool_rows(int mode, const float* x, int B, int S, int D, const int64_t* ids, int eos_id, const float* ln_w, const float* ln_b,
+                     float eps, const float* Wt, int P, int normalize, float* out, void* stream);
+/* the pooled row's attention output (att [rows, D], dtype) and residual row (planes -> fp32) copied to attp [B, D] / xp [B, D].
+ * cu == NULL: rows are [B, S]; cu int32 [B + 1]: packed rows, sample b's pooled row is cu[b + 1] - 1.  D % 8 == 0. */
+int plipmi_pool_gather(int dtype, const void* att, const void* hi, const void* lo, int B, int S, int D, const int64_t* ids, int eos_id,
+                       const int32_t* cu, void* attp, float* xp, void* stream);
+/* C [M, N] = scale * A [M, K] . W [N, K]^T, the exact-fp32 split-K MFMA kernel of the projection heads and the logits.  N, K % 32 == 0. */
+int plipmi_head_gemm(const float* A, const float* W, float* C, int M, int N, int K, float scale, void* stream);
 
 #ifdef __cplusplus
 }

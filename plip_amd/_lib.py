@@ -74,6 +74,14 @@ TEST_SYMBOLS = {
     "plipmi_qkv_attention": (_i, [_i, _vp, _vp, _vp, _vp, _i, _f, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "plipmi_resample_pos": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "plipmi_probe_loss_grad": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    "plipmi_attention_probs": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "plipmi_layernorm": (_i, [_vp, C.c_size_t, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "plipmi_layernorm_emit": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "plipmi_fold_ln": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "plipmi_text_embed_emit": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "plipmi_pool_rows": (_i, [_i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _i, _i, _vp, _vp]),
+    "plipmi_pool_gather": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "plipmi_head_gemm": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp]),
 }
 # every symbol include/plipmi.h declares (the product interface): (restype, argtypes)
 SYMBOLS = {

@@ -117,9 +117,12 @@ __device__ __forceinline__ float row8_sum(float v) {
 //         r = bits(x) - (hi << 16) lies in [-32768, 32767]; lo = round(r / 256) clamped to [-128, 127]:
 //         bits(x') = (hi << 16) + (lo << 8), |x' - x| <= 2^-16 |x| (8 + 8 significand bits; the operand plane itself keeps 8) --
 //         2^-15 in the corner r >= 32640, where the remainder rounds to +128 and is stored as +127 (0.2 % of values).
-//   f16:  hi = nearest f16 (ties to even, saturating at +-65504); lo = round((x - hi) / 2^(E - 18)) clamped to [-128, 127] with E the
+//   f16:  hi = nearest f16 (ties to even, saturating at +-65504); lo = round((x - hi) / 2^(E - 18)) clamped to [-127, 127] with E the
 //         exponent of hi (at least -14): x - hi is at most half an f16 ulp = 2^(E - 11) = 128 units.  |x' - x| <= 2^-19 |x|
-//         (11 + 8 bits) for 2^-14 <= |x| <= 65504; beyond, the stream saturates (the reference's own f16 CUDA path would hold inf).
+//         (11 + 8 bits) for 2^-14 <= |x| <= 65504, 2^-18 in the corners where the remainder rounds to +-128; beyond, the stream
+//         saturates (the reference's own f16 CUDA path would hold inf).  The clamp is symmetric on purpose: hi - 128 units is EXACTLY
+//         the midpoint of hi and its lower neighbour, and rounding that tie to even would hand a re-split of the joined value the
+//         other neighbour -- with +-127 the operand plane of split(join(hi, lo)) is hi again, as it is for bf16.
 // The stream is NOT the exact fp32 value any more: every residual update rounds it to 16 (bf16) / 19 (f16) significand bits -- three
 // orders of magnitude below the 2^-9 / 2^-12 rounding of the operands it feeds.  hi is always the correctly rounded operand of the
 // value the epilogue computed in fp32 (the remainder is rounded, never the operand).
@@ -154,7 +157,7 @@ template <> __device__ __forceinline__ void split_f32<f16_t>(float x, unsigned& 
   const f16_t h = (f16_t)sat_f16(x);
   const float hf = (float)h;
   const float scale = __builtin_bit_cast(float, (272u - f16_plane_exp(hf)) << 23);   // 2^(18 - E)
-  const float r = __builtin_amdgcn_fmed3f(__builtin_rintf((x - hf) * scale), -128.0f, 127.0f);
+  const float r = __builtin_amdgcn_fmed3f(__builtin_rintf((x - hf) * scale), -127.0f, 127.0f);
   hi16 = (unsigned)__builtin_bit_cast(unsigned short, h);
   lo8 = (unsigned)(int)r & 0xffu;
 }

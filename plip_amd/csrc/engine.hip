@@ -1412,6 +1412,7 @@ int plipmi_gemm_nt_ln(int dtype, int mode, int variant, int M, int N, int K, con
   if (dtype != PLIPMI_BF16 && dtype != PLIPMI_F16) return fail(PLIPMI_ERR_INVALID, "LayerNorm-folded epilogues are 16-bit-engine forms");
   if (mode < 0 || mode > 4 || M < 0 || N <= 0 || K <= 0 || !A || !W || !C || !bias) return fail(PLIPMI_ERR_INVALID, "bad argument");
   if (mode < 2 && (!stats || ns <= 0)) return fail(PLIPMI_ERR_INVALID, "mode 0/1 need the row statistics");
+  if (mode < 2 && ns % 2) return fail(PLIPMI_ERR_INVALID, "mode 0/1 read the statistics two slices at a time: ns = %d must be even (LayerNorm widths are multiples of 128)", ns);
   if (mode >= 2 && (!xb_out || !st_out || N % kLnSlice)) return fail(PLIPMI_ERR_INVALID, "mode 2/3 need xb_out, st_out and N % 64 == 0");
   if (mode >= 3 && variant == -3) return fail(PLIPMI_ERR_INVALID, "the small-M kernel has no split-plane epilogue");
   GemmParams p;
@@ -1499,6 +1500,84 @@ int plipmi_resample_pos(const float* src, float* dst, int n0, int gh, int gw, in
 int plipmi_check_async(plipmi_handle h) {
   if (!h) return fail(PLIPMI_ERR_INVALID, "null handle");
   return check_async(h);
+}
+
+// ---- kernel-level entries of the kernels around the GEMMs (plipmi_test.h): arguments checked here, then the engine's own launcher ----
+static bool half_code(int dtype) { return dtype == PLIPMI_BF16 || dtype == PLIPMI_F16; }
+
+int plipmi_attention_probs(int dtype, const void* qkv, float* probs, int B, int S, int H, int causal, const int64_t* key_mask,
+                           void* stream) {
+  if ((dtype != PLIPMI_F32 && !half_code(dtype)) || !qkv || !probs || B < 0 || S <= 0 || S > 1024 || H <= 0)
+    return fail(PLIPMI_ERR_INVALID, "bad argument (qkv, probs non-null, 1 <= S <= 1024, H >= 1)");
+  const hipError_t e = launch_attention_probs(qkv, probs, dtype, B, S, H, causal, key_mask, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(PLIPMI_ERR_HIP, "attention probabilities launch (S=%d) failed: %s", S, hipGetErrorString(e));
+  return PLIPMI_OK;
+}
+int plipmi_layernorm(const float* x, size_t x_row_stride, const float* g, const float* b, void* y, int y_dtype, int rows, int D,
+                     float eps, void* stream) {
+  if (!x || !g || !b || !y || rows < 0 || (y_dtype != PLIPMI_F32 && !half_code(y_dtype))) return fail(PLIPMI_ERR_INVALID, "bad argument");
+  if (D <= 0 || D % 4 || D > 2048 || x_row_stride % 4 || x_row_stride < (size_t)D)
+    return fail(PLIPMI_ERR_INVALID, "LayerNorm width %d / row stride %zu: D %% 4 == 0, D <= 2048, stride %% 4 == 0, stride >= D", D, x_row_stride);
+  if (y == (const void*)x && (y_dtype != PLIPMI_F32 || x_row_stride != (size_t)D))
+    return fail(PLIPMI_ERR_INVALID, "in place: fp32 rows of stride D only");
+  HIP_TRY(launch_layernorm(x, x_row_stride, g, b, y, y_dtype, rows, D, eps, reinterpret_cast<hipStream_t>(stream)));
+  return PLIPMI_OK;
+}
+int plipmi_layernorm_emit(int dtype, const float* x, const float* g, const float* b, void* hi, void* lo, float* st, int rows, int D,
+                          float eps, void* stream) {
+  if (!half_code(dtype) || !x || !g || !b || !hi || !lo || !st || rows < 0) return fail(PLIPMI_ERR_INVALID, "bad argument");
+  if (D <= 0 || D % kLnSlice || D > 2048) return fail(PLIPMI_ERR_INVALID, "width %d: D %% 64 == 0, D <= 2048", D);
+  HIP_TRY(launch_layernorm_emit(x, g, b, hi, lo, st, rows, D, eps, dtype, reinterpret_cast<hipStream_t>(stream)));
+  return PLIPMI_OK;
+}
+int plipmi_fold_ln(int dtype, const float* W, const float* bias, const float* g, const float* b, void* Wf, float* c2, int rows, int K,
+                   float pre, void* stream) {
+  if (!half_code(dtype) || !W || !bias || !g || !b || !Wf || !c2 || rows < 0 || K <= 0 || K % 4)
+    return fail(PLIPMI_ERR_INVALID, "bad argument (16-bit dtype, K %% 4 == 0)");
+  HIP_TRY(launch_fold_ln(W, bias, g, b, Wf, c2, rows, K, pre, dtype, reinterpret_cast<hipStream_t>(stream)));
+  return PLIPMI_OK;
+}
+int plipmi_text_embed_emit(int dtype, int packed, const int64_t* ids, const float* tok, const float* pos, void* hi, void* lo, float* st,
+                           int B, int S, int D, int vocab, int eos_id, int32_t* cu, int32_t* rowmap, int32_t* m, int32_t* bad_id,
+                           void* stream) {
+  if (!half_code(dtype) || !ids || !tok || !pos || !hi || !lo || !st || B < 0 || S <= 0 || vocab <= 0 || (packed != 0 && packed != 1))
+    return fail(PLIPMI_ERR_INVALID, "bad argument");
+  if (D <= 0 || D % kLnSlice) return fail(PLIPMI_ERR_INVALID, "width %d: D %% 64 == 0", D);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (!packed) {
+    HIP_TRY(launch_text_embed_emit(ids, tok, pos, hi, lo, st, B, S, D, vocab, bad_id, dtype, s));
+    return PLIPMI_OK;
+  }
+  if (!cu || !rowmap || !m) return fail(PLIPMI_ERR_INVALID, "the packed form returns cu [B + 1], rowmap [B * S] and m [1]");
+  if (S > 256 || (size_t)(B + 1) * sizeof(int) > 64 * 1024) return fail(PLIPMI_ERR_INVALID, "packing: S <= 256, B + 1 <= 16384 (got S=%d B=%d)", S, B);
+  HIP_TRY(launch_text_pack(ids, B, S, eos_id, cu, rowmap, m, s));
+  HIP_TRY(launch_text_embed_emit_packed(ids, tok, pos, hi, lo, st, rowmap, m, B * S, S, D, vocab, bad_id, dtype, s));
+  return PLIPMI_OK;
+}
+int plipmi_pool_rows(int mode, const float* x, int B, int S, int D, const int64_t* ids, int eos_id, const float* ln_w, const float* ln_b,
+                     float eps, const float* Wt, int P, int normalize, float* out, void* stream) {
+  if ((mode != 0 && mode != 1) || !x || !ln_w || !ln_b || !out || B < 0 || S <= 0 || D <= 0) return fail(PLIPMI_ERR_INVALID, "bad argument");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (mode == 0) {
+    if (!Wt || P <= 0 || P > 1024 || D > 2048) return fail(PLIPMI_ERR_INVALID, "pooled head: D <= 2048, 1 <= P <= 1024 (got D=%d P=%d)", D, P);
+    HIP_TRY(launch_pool_head(x, S, D, ids, eos_id, ln_w, ln_b, eps, Wt, P, out, B, normalize, s));
+    return PLIPMI_OK;
+  }
+  if (D % 4 || D > 2048) return fail(PLIPMI_ERR_INVALID, "pooled LayerNorm: D %% 4 == 0, D <= 2048 (got %d)", D);
+  HIP_TRY(launch_pool_layernorm(x, S, D, ids, eos_id, ln_w, ln_b, eps, out, B, s));
+  return PLIPMI_OK;
+}
+int plipmi_pool_gather(int dtype, const void* att, const void* hi, const void* lo, int B, int S, int D, const int64_t* ids, int eos_id,
+                       const int32_t* cu, void* attp, float* xp, void* stream) {
+  if (!half_code(dtype) || !att || !hi || !lo || !attp || !xp || B < 0 || S <= 0 || D <= 0 || D % 8)
+    return fail(PLIPMI_ERR_INVALID, "bad argument (16-bit dtype, D %% 8 == 0)");
+  HIP_TRY(launch_pool_gather(att, hi, lo, S, D, ids, eos_id, attp, xp, B, dtype, reinterpret_cast<hipStream_t>(stream), cu));
+  return PLIPMI_OK;
+}
+int plipmi_head_gemm(const float* A, const float* W, float* C, int M, int N, int K, float scale, void* stream) {
+  if (!A || !W || !C || M < 0 || N <= 0 || K <= 0 || N % 32 || K % 32) return fail(PLIPMI_ERR_INVALID, "bad argument (N %% 32 == 0, K %% 32 == 0)");
+  HIP_TRY(launch_head_gemm(A, W, C, M, N, K, reinterpret_cast<hipStream_t>(stream), scale));
+  return PLIPMI_OK;
 }
 int plipmi_recode_planes(void* hi, void* lo, size_t rows, int D, int from_dtype, int to_dtype, void* stream) {
   if (!hi || !lo || D <= 0 || D % 8) return fail(PLIPMI_ERR_INVALID, "null planes / width not a multiple of 8");

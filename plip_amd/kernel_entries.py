@@ -139,7 +139,7 @@ def split_planes(x: torch.Tensor, dtype=torch.bfloat16):
     arithmetic, bit for bit what the kernels write: ``hi`` [M, N] in the operand type, ``lo`` = uint8 [lo_plane_bytes(M, N)] in the
     blocked layout (padding bytes zero).
     bf16: hi = nearest bf16 (ties away from zero); r = bits(x) - (hi << 16) in [-32768, 32767]; lo = min((r + 128) >> 8, 127).
-    f16:  hi = nearest f16 (ties to even, saturating); lo = clamp(rint((x - hi) * 2^(18 - E(hi))), -128, 127), E >= -14."""
+    f16:  hi = nearest f16 (ties to even, saturating); lo = clamp(rint((x - hi) * 2^(18 - E(hi))), -127, 127), E >= -14 (symmetric: split(join(hi, lo)) gives hi back)."""
     assert x.dim() == 2
     M, N = x.shape
     if dtype == torch.bfloat16:
@@ -155,7 +155,7 @@ def split_planes(x: torch.Tensor, dtype=torch.bfloat16):
         hi16 = xc.clamp(-65504.0, 65504.0).to(torch.float16)
         hf = hi16.float()
         eb = ((hf.view(torch.int32) >> 23) & 0xFF).clamp(min=113)
-        lo = torch.round((xc.double() - hf.double()) * _pow2(145 - eb)).clamp(-128, 127).to(torch.int64)   # exact power-of-two scaling, ties to even
+        lo = torch.round((xc.double() - hf.double()) * _pow2(145 - eb)).clamp(-127, 127).to(torch.int64)   # exact power-of-two scaling, ties to even
     plane = torch.zeros(lo_plane_bytes(M, N), dtype=torch.uint8, device=x.device)
     plane[lo_plane_index(M, N, x.device).reshape(-1)] = (lo & 0xFF).to(torch.uint8).reshape(-1)
     return hi16, plane
@@ -234,3 +234,159 @@ def probe_loss_grad(engine, x: torch.Tensor, y: torch.Tensor, wb: torch.Tensor, 
                                               _ptr(loss), _ptr(grad), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
                    "plipmi_probe_loss_grad")
     return loss, grad
+
+
+# ---- the kernels around the GEMMs (include/plipmi_test.h, tests/test_gpu_small_kernels.py) ---------------------------------------------
+def _stream(t: torch.Tensor):
+    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _f32(*ts):
+    for t in ts:
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+
+
+def attention_probs(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool = False, key_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``plipmi_attention_probs``: qkv [B*S, 3*H*64] (fp32 / bf16 / f16, scale folded into q) -> fp32 probabilities [B, H, S, S]."""
+    lib = _lib.load()
+    assert qkv.is_cuda and qkv.is_contiguous() and qkv.shape == (B * S, 3 * H * 64)
+    assert key_mask is None or (key_mask.is_cuda and key_mask.dtype == torch.int64 and key_mask.is_contiguous() and key_mask.shape == (B, S))
+    probs = torch.empty((B, H, S, S) if S <= 1024 else (1,), dtype=torch.float32, device=qkv.device)   # S > 1024 is refused before any launch
+    with torch.cuda.device(qkv.device):
+        _lib.check(lib.plipmi_attention_probs(_code(qkv.dtype), _ptr(qkv), _ptr(probs), B, S, H, int(causal), _ptr(key_mask), _stream(qkv)),
+                   "plipmi_attention_probs")
+    return probs
+
+
+def layernorm(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: float = 1e-5, out_dtype=torch.float32, inplace: bool = False) -> torch.Tensor:
+    """``plipmi_layernorm``: x fp32 [rows, D], possibly a strided view of a wider buffer (row stride and storage offset multiples of 4
+    elements, unit column stride) -> contiguous [rows, D] of ``out_dtype``; ``inplace``: y is x itself (contiguous fp32 rows)."""
+    lib = _lib.load()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and (x.shape[1] == 1 or x.stride(1) == 1)
+    _f32(g, b)
+    rows, D = x.shape
+    assert g.numel() == D and b.numel() == D
+    xs = x.stride(0) if rows > 1 else D
+    if inplace:
+        assert x.is_contiguous() and out_dtype == torch.float32
+        y = x
+    else:
+        y = torch.empty((rows, D), dtype=out_dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.plipmi_layernorm(_ptr(x), xs, _ptr(g), _ptr(b), _ptr(y), _code(out_dtype), rows, D, float(eps), _stream(x)),
+                   "plipmi_layernorm")
+    return y
+
+
+def layernorm_emit(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, dtype, eps: float = 1e-5):
+    """``plipmi_layernorm_emit``: x fp32 [rows, D] -> (hi [rows, D] of ``dtype``, lo uint8 [lo_plane_bytes], st fp32 [rows, D // 64, 2])."""
+    lib = _lib.load()
+    _f32(x, g, b)
+    rows, D = x.shape
+    assert g.numel() == D and b.numel() == D
+    hi = torch.empty((rows, D), dtype=dtype, device=x.device)
+    lo = torch.zeros(lo_plane_bytes(rows, D), dtype=torch.uint8, device=x.device)
+    st = torch.empty((rows, max(D // 64, 1), 2), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.plipmi_layernorm_emit(_code(dtype), _ptr(x), _ptr(g), _ptr(b), _ptr(hi), _ptr(lo), _ptr(st), rows, D, float(eps),
+                                             _stream(x)), "plipmi_layernorm_emit")
+    return hi, lo, st
+
+
+def fold_ln(w: torch.Tensor, bias: torch.Tensor, g: torch.Tensor, b: torch.Tensor, dtype, pre: float = 1.0):
+    """``plipmi_fold_ln``: W fp32 [rows, K], bias [rows], LayerNorm gain / bias [K] -> (Wf [rows, K] of ``dtype``, c2 fp32 [rows])."""
+    lib = _lib.load()
+    _f32(w, bias, g, b)
+    rows, K = w.shape
+    assert bias.numel() == rows and g.numel() == K and b.numel() == K
+    wf = torch.empty((rows, K), dtype=dtype, device=w.device)
+    c2 = torch.empty((rows,), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _lib.check(lib.plipmi_fold_ln(_code(dtype), _ptr(w), _ptr(bias), _ptr(g), _ptr(b), _ptr(wf), _ptr(c2), rows, K, float(pre), _stream(w)),
+                   "plipmi_fold_ln")
+    return wf, c2
+
+
+def text_embed_emit(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, dtype, packed: bool = False, eos_id: int = -1):
+    """``plipmi_text_embed_emit``: ids int64 [B, S], tok fp32 [vocab, D], pos fp32 [>= S, D] -> (hi, lo, st) of the [B*S, D] rows; with
+    ``packed`` the pack plan runs first and the result is (hi, lo, st, cu int32 [B + 1], rowmap int32 [B*S], m int32 [1]): only rows
+    0 .. m-1 of the planes / statistics and entries 0 .. m-1 of rowmap are written (rowmap starts zeroed)."""
+    lib = _lib.load()
+    assert ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and ids.dim() == 2
+    _f32(tok, pos)
+    B, S = ids.shape
+    vocab, D = tok.shape
+    assert pos.shape[1] == D and pos.shape[0] >= S
+    dev = ids.device
+    hi = torch.zeros((B * S, D), dtype=dtype, device=dev)
+    lo = torch.zeros(lo_plane_bytes(B * S, D), dtype=torch.uint8, device=dev)
+    st = torch.zeros((B * S, max(D // 64, 1), 2), dtype=torch.float32, device=dev)
+    cu = rowmap = m = None
+    if packed:
+        cu = torch.zeros((B + 1,), dtype=torch.int32, device=dev)
+        rowmap = torch.zeros((B * S,), dtype=torch.int32, device=dev)
+        m = torch.zeros((1,), dtype=torch.int32, device=dev)
+    bad = torch.zeros((1,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.plipmi_text_embed_emit(_code(dtype), int(packed), _ptr(ids), _ptr(tok), _ptr(pos), _ptr(hi), _ptr(lo), _ptr(st), B, S, D,
+                                              vocab, int(eos_id), _ptr(cu), _ptr(rowmap), _ptr(m), _ptr(bad), _stream(ids)),
+                   "plipmi_text_embed_emit")
+    assert int(bad.item()) == 0, "token id outside the vocabulary"
+    return (hi, lo, st, cu, rowmap, m) if packed else (hi, lo, st)
+
+
+def pool_rows(x: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, ids: Optional[torch.Tensor] = None, eos_id: int = -1,
+              wt: Optional[torch.Tensor] = None, normalize: bool = False, eps: float = 1e-5) -> torch.Tensor:
+    """``plipmi_pool_rows``: x fp32 [B, S, D] -> LayerNorm of the pooled row (row 0, or the EOS row of ``ids`` int64 [B, S]); with
+    ``wt`` fp32 [D, P] (the projection transposed) the pooled head [B, P] (mode 0), without it the LayerNorm'd row [B, D] (mode 1)."""
+    lib = _lib.load()
+    _f32(x, ln_w, ln_b)
+    B, S, D = x.shape
+    assert ln_w.numel() == D and ln_b.numel() == D
+    assert ids is None or (ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and ids.shape == (B, S))
+    P = 0
+    if wt is not None:
+        _f32(wt)
+        assert wt.shape[0] == D
+        P = wt.shape[1]
+    out = torch.empty((B, P if wt is not None else D), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.plipmi_pool_rows(0 if wt is not None else 1, _ptr(x), B, S, D, _ptr(ids), int(eos_id), _ptr(ln_w), _ptr(ln_b), float(eps),
+                                        _ptr(wt), P, int(normalize), _ptr(out), _stream(x)), "plipmi_pool_rows")
+    return out
+
+
+def pool_gather(att: torch.Tensor, hi: torch.Tensor, lo: torch.Tensor, B: int, S: int, ids: Optional[torch.Tensor] = None, eos_id: int = -1,
+                cu: Optional[torch.Tensor] = None):
+    """``plipmi_pool_gather``: att [rows, D] (16-bit) and the planes (hi [rows, D], lo) -> (attp [B, D], xp fp32 [B, D]) of each sample's
+    pooled row; rows = B * S, or cu[B] packed rows with ``cu`` int32 [B + 1] (every cu[b + 1] - 1 must be a row of the buffers)."""
+    lib = _lib.load()
+    rows, D = att.shape
+    assert att.is_cuda and att.is_contiguous() and hi.is_contiguous() and lo.is_contiguous() and hi.dtype == att.dtype
+    assert hi.shape == (rows, D) and lo.dtype == torch.uint8 and lo.numel() == lo_plane_bytes(rows, D)
+    assert ids is None or (ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and ids.shape == (B, S))
+    if cu is not None:
+        assert cu.is_cuda and cu.dtype == torch.int32 and cu.shape == (B + 1,)
+        c = cu.cpu()
+        assert int(c[1:].min()) >= 1 and int(c.max()) <= rows
+    else:
+        assert rows == B * S
+    attp = torch.empty((B, D), dtype=att.dtype, device=att.device)
+    xp = torch.empty((B, D), dtype=torch.float32, device=att.device)
+    with torch.cuda.device(att.device):
+        _lib.check(lib.plipmi_pool_gather(_code(att.dtype), _ptr(att), _ptr(hi), _ptr(lo), B, S, D, _ptr(ids), int(eos_id), _ptr(cu), _ptr(attp),
+                                          _ptr(xp), _stream(att)), "plipmi_pool_gather")
+    return attp, xp
+
+
+def head_gemm(a: torch.Tensor, w: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """``plipmi_head_gemm``: scale * a [M, K] @ w [N, K]^T in fp32 (split-K MFMA kernel of the heads and the logits)."""
+    lib = _lib.load()
+    _f32(a, w)
+    M, K = a.shape
+    N = w.shape[0]
+    assert w.shape[1] == K
+    out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(lib.plipmi_head_gemm(_ptr(a), _ptr(w), _ptr(out), M, N, K, float(scale), _stream(a)), "plipmi_head_gemm")
+    return out

@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+from small_kernel_refs import slice_stats as _slice_stats   # per-64-column {sum, centred M2}, shared with the small-kernel tests
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 256, 64), (37, 256, 128), (128, 256, 192), (300, 512, 768), (515, 256, 3072),
@@ -143,15 +145,6 @@ def test_operands_of_four_gib_take_the_64bit_address_kernels():
 
 
 # ---- LayerNorm folded into the GEMMs (gemm.h EPI_BIAS_LN / EPI_QGELU_LN / EPI_RESID_EMIT) ---------------------------
-def _slice_stats(x):
-    """per-row partials over 64-column slices: {sum, centred M2} -- what the producers emit"""
-    M, D = x.shape
-    xs = x.double().reshape(M, D // 64, 64)
-    s = xs.sum(-1)
-    m2 = ((xs - s[..., None] / 64) ** 2).sum(-1)
-    return torch.stack((s, m2), dim=-1).float().contiguous()
-
-
 @pytest.mark.parametrize("hdt", list(HALF.values()), ids=list(HALF))
 @pytest.mark.parametrize("variant", list(range(NVAR)) + [-1, -3])
 @pytest.mark.parametrize("mode", [0, 1])

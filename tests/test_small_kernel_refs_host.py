@@ -1,0 +1,177 @@
+"""The float64 references of tests/small_kernel_refs.py against independent formulations, on the CPU: the GPU test
+(tests/test_gpu_small_kernels.py) measures the kernels against these references, so they are pinned here first --
+torch.nn.functional, numpy and oracle/clip_oracle.py never enter the references themselves."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import small_kernel_refs as R
+from oracle import clip_oracle as O
+
+
+def _gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+@pytest.mark.parametrize("D", [4, 252, 768, 1664])
+def test_layer_norm_matches_torch(D):
+    g0 = _gen(D)
+    x = (torch.randn(7, D, generator=g0) + 1.5).double()
+    x[:, 1] += 60.0
+    g, b = torch.randn(D, generator=g0).double(), torch.randn(D, generator=g0).double()
+    want = F.layer_norm(x, (D,), g, b, 1e-5)
+    assert (R.layer_norm(x, g, b, 1e-5) - want).abs().max().item() < 1e-12
+    const = torch.full((2, D), 3.25, dtype=torch.float64)                 # variance 0: the output is beta
+    assert (R.layer_norm(const, g, b, 1e-5) - b).abs().max().item() < 1e-12
+
+
+def test_slice_stats_recombine_to_the_row_statistics():
+    """Chan's formula over the 64-column partials gives the row's mean and variance"""
+    x = torch.randn(5, 256, generator=_gen(1)).double() * 3 + 11
+    st = R.slice_stats(x).double()
+    mean = st[..., 0].sum(-1) / 256
+    m2 = st[..., 1].sum(-1) + (64 * (st[..., 0] / 64 - mean[:, None]) ** 2).sum(-1)
+    assert (mean - x.mean(-1)).abs().max().item() < 1e-5
+    assert (m2 / 256 - x.var(-1, unbiased=False)).abs().max().item() < 1e-4
+
+
+@pytest.mark.parametrize("pre", [1.0, 0.125])
+def test_folded_weights_are_layernorm_then_linear(pre):
+    """rstd * (x . Wf^T) + c2 == pre * Linear(LayerNorm(x)): the centred rows subtract the mean"""
+    g0 = _gen(3)
+    D, N = 260, 9
+    x = torch.randn(6, D, generator=g0).double() + 1.5
+    W, bias = torch.randn(N, D, generator=g0).double(), torch.randn(N, generator=g0).double()
+    g = torch.exp(torch.empty(D).uniform_(-2.3, 2.3, generator=g0)).double()
+    b = torch.randn(D, generator=g0).double()
+    Wf, c2 = R.fold_ln(W, bias, g, b, pre)
+    assert Wf.sum(1).abs().max().item() < 1e-12
+    rstd = 1.0 / torch.sqrt(x.var(-1, unbiased=False, keepdim=True) + 1e-5)
+    want = pre * F.linear(F.layer_norm(x, (D,), g, b, 1e-5), W, bias)
+    assert (rstd * (x @ Wf.T) + c2 - want).abs().max().item() < 1e-11
+
+
+@pytest.mark.parametrize("causal,kind", [(False, None), (True, None), (True, "pad"), (True, "holes"), (False, "holes"), (True, "key0"),
+                                         (True, "empty")])
+def test_attention_probs_match_the_additive_mask_softmax(causal, kind):
+    B, S, H = 2, 19, 3
+    g0 = _gen(S)
+    qkv = torch.randn(B * S, 3 * H * 64, generator=g0).double()
+    mask = None
+    if kind == "pad":
+        mask = (torch.arange(S)[None, :] < torch.tensor([[7], [19]])).long()
+    elif kind == "holes":
+        mask = (torch.rand(B, S, generator=g0) < 0.6).long()
+        mask[:, 3], mask[:, 4] = 0, 1
+    elif kind == "key0":
+        mask = torch.ones(B, S, dtype=torch.long)
+        mask[0, :5] = 0
+    elif kind == "empty":
+        mask = torch.ones(B, S, dtype=torch.long)
+        mask[1] = 0
+    p = R.attention_probs(qkv, B, S, H, causal, mask)
+    x = qkv.reshape(B, S, 3, H, 64)
+    q, k = x[:, :, 0].permute(0, 2, 1, 3), x[:, :, 1].permute(0, 2, 1, 3)
+    add = torch.zeros(B, 1, S, S, dtype=torch.float64)
+    if causal:
+        add = add + torch.triu(torch.full((S, S), float("-inf"), dtype=torch.float64), 1)
+    if mask is not None:
+        add = add.masked_fill((mask == 0)[:, None, None, :], float("-inf"))
+    want = torch.softmax(q @ k.transpose(-1, -2) + add, dim=-1)         # NaN where a row has no live key
+    live = R.live_keys(B, S, causal, mask)
+    has = live.any(-1)[:, None, :].expand(B, H, S)
+    assert torch.isnan(want[~has]).all() and (p[~has] == 0).all()
+    assert (p[has] - want[has]).abs().max().item() < 1e-14
+    assert (p[~live[:, None].expand(B, H, S, S)] == 0).all()
+    if kind == "key0":
+        assert not has[0, :, :5].any() and has[0, :, 5:].all() and has[1].all()
+    if kind == "empty":
+        assert not has[1].any()
+
+
+def test_embed_rows_match_embedding():
+    g0 = _gen(5)
+    tok, pos = torch.randn(50, 64, generator=g0), torch.randn(9, 64, generator=g0)
+    ids = torch.randint(0, 50, (3, 7), generator=g0)
+    want = (F.embedding(ids, tok) + pos[:7][None]).reshape(21, 64)
+    assert torch.equal(R.embed_rows(ids, tok, pos, torch.float32), want)
+    assert torch.equal(R.embed_rows(ids, tok, pos), (F.embedding(ids, tok.double()) + pos[:7].double()[None]).reshape(21, 64))
+
+
+def _captions(vocab, S, gen):
+    ids = torch.randint(3, vocab - 1, (8, S), generator=gen)
+    ids[0, 0] = vocab - 1                                    # EOS first
+    ids[1, S - 1] = vocab - 1                                # EOS last
+    ids[3, 2] = ids[3, S - 2] = vocab - 1                    # two EOS: the first counts          (row 2: none)
+    ids[4] = torch.randint(3, 20, (S,), generator=gen)
+    ids[4, 1] = ids[4, 3] = 30                               # the maximum twice, no EOS
+    ids[5:, S // 2] = vocab - 1
+    return ids
+
+
+@pytest.mark.parametrize("S", [5, 77])
+def test_eos_rules_and_pack_plan(S):
+    vocab = 100
+    ids = _captions(vocab, S, _gen(S))
+    first = R.eos_positions(ids, vocab - 1)
+    assert torch.equal(first, (ids == vocab - 1).int().argmax(-1))          # HF: first position of eos, 0 when absent
+    assert first.tolist()[:5] == [0, S - 1, 0, 2, 0]
+    for legacy in (2, -1):
+        got = R.eos_positions(ids, legacy)
+        assert torch.equal(got, ids.argmax(-1)) and np.array_equal(got.numpy(), O.eos_positions(ids.numpy(), legacy))
+        assert got[4] == 1
+    assert np.array_equal(first.numpy(), O.eos_positions(ids.numpy(), vocab - 1))
+    ln, cu, rowmap = R.pack_plan(ids, vocab - 1)
+    assert torch.equal(ln.long(), first + 1) and torch.equal(cu.long(), torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(first + 1, 0)]))
+    b = torch.repeat_interleave(torch.arange(8), ln.long())
+    s = torch.arange(int(cu[-1])) - cu.long()[b]
+    assert torch.equal(rowmap.long(), (b << 8) | s) and ln[2] == 1
+
+
+@pytest.mark.parametrize("eos_id", [None, 99, 2])
+@pytest.mark.parametrize("normalize", [False, True])
+def test_pooled_head_matches_the_oracle(eos_id, normalize):
+    """oracle/clip_oracle.py text_tower / vision_tower tail: LayerNorm of EVERY row, then the pick, then the projection"""
+    g0 = _gen(7)
+    B, S, D, P = 8, 9, 64, 40
+    x = torch.randn(B, S, D, generator=g0).double() * 2 + 0.5
+    w, b = torch.randn(D, generator=g0).double(), torch.randn(D, generator=g0).double()
+    W = torch.randn(P, D, generator=g0).double()
+    ids = None if eos_id is None else _captions(100, S, g0)
+    got = R.pooled_head(x, ids, eos_id if eos_id is not None else -1, w, b, 1e-5, W, normalize)
+    ln = O.layer_norm(x.numpy(), w.numpy(), b.numpy(), 1e-5)
+    pos = np.zeros(B, np.int64) if ids is None else O.eos_positions(ids.numpy(), eos_id)
+    want = ln[np.arange(B), pos] @ W.numpy().T
+    if normalize:
+        want = O.l2_normalize(want)
+    assert np.abs(got.numpy() - want).max() < 1e-12
+    assert np.abs(R.pooled_head(x, ids, eos_id if eos_id is not None else -1, w, b, 1e-5).numpy() - ln[np.arange(B), pos]).max() < 1e-12
+
+
+def test_topk_and_first_argmax_match_numpy():
+    rs = np.random.RandomState(11)
+    sc = rs.randint(-3, 4, size=(6, 300)).astype(np.float32)                # many ties
+    sc[0, 5:40] = -np.inf
+    sc[1, 7] = sc[1, 250] = np.inf
+    sc[2, ::7] = np.nan
+    clean = np.where(np.isnan(sc), -np.inf, sc)
+    for k in (1, 50, 300):
+        np.testing.assert_array_equal(R.topk_stable(sc, k), np.argsort(-clean, axis=1, kind="stable")[:, :k])
+    np.testing.assert_array_equal(R.first_argmax(clean), np.argmax(clean, axis=1))
+    tie = np.zeros((3, 130), np.float32)
+    tie[0, [63, 64]] = 2.0
+    tie[1, [5, 69]] = 2.0
+    tie[2, 129] = 1.0
+    assert R.first_argmax(tie).tolist() == [63, 5, 129] == np.argmax(tie, axis=1).tolist()
+
+
+def test_tolerance_helpers():
+    assert R.ulp32(1.0) == 2.0 ** -23 and R.ulp32(3.0) == 2.0 ** -22
+    ref = torch.tensor([1.0, 3.0, 0.0], dtype=torch.float64)
+    assert R.ulp16(ref, torch.bfloat16)[:2].tolist() == [2.0 ** -8, 3 * 2.0 ** -8] and R.ulp16(ref, torch.float16)[2].item() == 2.0 ** -24
+    cpu = torch.tensor([1.0 + 2.0 ** -20, 3.0, 0.0])
+    bound, err = R.fp32_bound(cpu, ref)
+    assert abs(err - 2.0 ** -20) < 1e-12 and bound == 4 * err
+    assert R.fp32_bound(ref.float(), ref)[0] == R.ulp32(3.0)                # floor: one fp32 ulp of the largest magnitude
+    assert R.fp32_bound(cpu, ref, cap=1e-7)[0] == 1e-7
