@@ -30,6 +30,8 @@ from plip_amd.reproducibility import EmbedderFactory, ImageRetrieval, LinearProb
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=2048)
+    ap.add_argument("--mixed-sizes", action="store_true",
+                    help="every image gets a size of its own (150..400 px per side) and the GPU resizes the ragged batches (ragged_resize=True)")
     ap.add_argument("--classes", type=int, default=8)
     ap.add_argument("--size", default="300x260", help="HxW of the synthetic images")
     ap.add_argument("--arch", default="ViT-B/32")
@@ -49,13 +51,16 @@ def main():
     embedder = EmbedderFactory().factory(argparse.Namespace(model_name="plip", backbone=ck, dtype=args.dtype, max_batch=256))
 
     rng = np.random.RandomState(0)
-    images = [rng.randint(0, 256, (h, w, 3), dtype=np.uint8) for _ in range(args.images)]
+    if args.mixed_sizes:       # what the reference's datasets hand over outside Kather: sizes that differ from file to file
+        images = [rng.randint(0, 256, (int(a), int(b), 3), dtype=np.uint8) for a, b in rng.randint(150, 401, (args.images, 2))]
+    else:
+        images = [rng.randint(0, 256, (h, w, 3), dtype=np.uint8) for _ in range(args.images)]
     ids, _ = W.synthetic_ids(cfg, args.images, 1, pad="zero")            # one synthetic caption per image (clip.tokenize-style)
     prompts, _ = W.synthetic_ids(cfg, args.classes, 2, pad="zero")       # class prompts
     labels = [f"class_{i}" for i in range(args.classes)]
 
     from plip_amd.plip import PLIP
-    plip = PLIP(model=embedder.model)                                     # same engine, the PLIP-class surface
+    plip = PLIP(model=embedder.model, ragged_resize=args.mixed_sizes)      # same engine, the PLIP-class surface
     t0 = time.perf_counter()
     raw = plip.encode_images(images, batch_size=256)                      # GPU resize + crop + normalise + tower
     img = raw / np.linalg.norm(raw, axis=1, keepdims=True)                # embedders/plip.py:53
@@ -64,7 +69,7 @@ def main():
     cls = embedder.text_embedder(prompts, batch_size=256, additional_cache_name="prompts")
     again = embedder.text_embedder(ids, batch_size=256, additional_cache_name="captions")   # cache hit
     assert np.array_equal(txt, again)
-    print(f"embedded {args.images} {h}x{w} images in {t1 - t0:.2f} s ({args.images / (t1 - t0):.0f} img/s incl. host loop and H2D), "
+    print(f"embedded {args.images} {'mixed-size' if args.mixed_sizes else f'{h}x{w}'} images in {t1 - t0:.2f} s ({args.images / (t1 - t0):.0f} img/s incl. host loop and H2D), "
           f"{args.images + args.classes} captions; cache folder {os.environ['PC_CACHE_FOLDER']}")
 
     target = [labels[i % args.classes] for i in range(args.images)]       # arbitrary targets: random weights know nothing

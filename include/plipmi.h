@@ -13,6 +13,8 @@
  *                            self.model.encode_image(images)                  reproducibility/embedders/plip.py:48
  *   plipmi_encode_image_u8<- self.preprocess(images=...) + get_image_features           plip.py:32-35,50
  *   plipmi_resize_crop_u8 <- Resize(n_px, bicubic) + CenterCrop(n_px)                  reproducibility/embedders/transform.py:45-48
+ *   plipmi_resize_crop_u8_ragged <- the same two steps on images whose sizes differ     transform.py:45-48, plip.py:32-35,
+ *                            (CLIPImageDataset: any file through _transform)           reproducibility/dataset_loading/internal_datasets.py:42
  *   plipmi_encode_text    <- self.model.get_text_features(**batch)            plip.py:68
  *                            self.model.encode_text(clip.tokenize(...))       reproducibility/embedders/plip.py:65-66
  *   plipmi_l2_normalize   <- x / np.linalg.norm(x, axis=-1, keepdims=True)    plip.py:75, embedders/plip.py:53,73
@@ -310,6 +312,25 @@ int plipmi_topk(plipmi_handle h, const float* scores, int N, int M, int k, int64
 int plipmi_resize_crop_u8(plipmi_handle h, const uint8_t* src, int B, int H, int W, int n_px, const int32_t* xbounds,
                           const int32_t* xcoef, int xksize, int left, const int32_t* ybounds, const int32_t* ycoef,
                           int yksize, int top, int row0, int nrows, uint8_t* tmp, uint8_t* dst, void* stream);
+
+/* The same resize + centre crop for a RAGGED batch: B uint8 RGB images, each with its own height and width, packed in one
+ * device buffer -- image b is hw[b] = {height, width} rows of width * 3 bytes at src + offsets[b].  dst [B,n_px,n_px,3] is
+ * bit-identical, image by image, to Image.resize((nw,nh), BICUBIC).crop(...) with the geometry of plipmi_resize_crop_u8's caller
+ * (shortest edge -> n_px, long edge int(n_px * long / short), crop_rule 0 = torchvision CenterCrop, 1 = HF center_crop).  Nothing
+ * per size is built on the host: Pillow's coefficient tables (float64, unfused) are computed on the device, in `workspace`.
+ *   offsets int64 [B], hw int32 [B,2]   device buffers;  offsets_host, hw_host: host copies of the same values, read during the
+ *                                        call only -- every check below and the sizing of the intermediate use them
+ *   ksize      taps the coefficient rows hold: at least 2 * ceil(2 * max(s, 1)) + 1 for the largest in / out ratio s of any axis
+ *              of the batch
+ *   workspace  device scratch of at least the workspace function's bytes for the same (hw_host, B, n_px, ksize), caller-owned (tables
+ *              + the horizontally filtered rows); nothing is allocated here and nothing synchronises: four kernel launches
+ * PLIPMI_ERR_INVALID before any launch: a side < 1, an in / out ratio above 64, offsets[b] + height * width * 3 > src_bytes,
+ * B > 65535, ksize or workspace_bytes too small.  B = 0 launches nothing. */
+int plipmi_resize_crop_u8_ragged(plipmi_handle h, const uint8_t* src, size_t src_bytes, const int64_t* offsets, const int32_t* hw,
+                                 const int64_t* offsets_host, const int32_t* hw_host, int B, int n_px, int crop_rule, int ksize,
+                                 void* workspace, size_t workspace_bytes, uint8_t* dst, void* stream);
+/* bytes of `workspace` for that call (0 for a bad argument); host arithmetic only */
+size_t plipmi_resize_ragged_workspace(const int32_t* hw_host, int B, int n_px, int ksize);
 
 /* Fused similarity + top-k: for every row q of keys [Nq,D] the k rows j of space [Ns,D] with the largest <q, space_j>,
  * descending (ties: lower j first), WITHOUT materialising the [Nq,Ns] score matrix: scores are produced in

@@ -147,6 +147,13 @@ int plipmi_pool_gather(int dtype, const void* att, const void* hi, const void* l
 /* C [M, N] = scale * A [M, K] . W [N, K]^T, the exact-fp32 split-K MFMA kernel of the projection heads and the logits.  N, K % 32 == 0. */
 int plipmi_head_gemm(const float* A, const float* W, float* C, int M, int N, int K, float scale, void* stream);
 
+/* The table kernel of the ragged resize (csrc/resize_ragged.hip) on its own, one axis resampled from in_size to out_size pixels:
+ * Pillow's 8-bit bicubic tables for outputs first .. first + count -- bounds int32 [count, 2] = (first input index, taps), coef int32
+ * [count, ksize] 22-bit fixed-point weights, zero past the taps (device buffers) -- to compare, integer for integer, with
+ * plip_amd/preprocess.py resample_coeffs.  in_size / out_size <= 64, ksize >= 2 * ceil(2 * max(in_size / out_size, 1)) + 1. */
+int plipmi_resize_ragged_tables(int in_size, int out_size, int first, int count, int ksize, int32_t* bounds, int32_t* coef,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

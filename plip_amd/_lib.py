@@ -82,6 +82,7 @@ TEST_SYMBOLS = {
     "plipmi_pool_rows": (_i, [_i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _i, _i, _vp, _vp]),
     "plipmi_pool_gather": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "plipmi_head_gemm": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "plipmi_resize_ragged_tables": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 # every symbol include/plipmi.h declares (the product interface): (restype, argtypes)
 SYMBOLS = {
@@ -104,6 +105,8 @@ SYMBOLS = {
     "plipmi_logits": (_i, [_vp, _vp, _i, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "plipmi_topk": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "plipmi_resize_crop_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "plipmi_resize_crop_u8_ragged": (_i, [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_size_t, _vp, _vp]),
+    "plipmi_resize_ragged_workspace": (C.c_size_t, [_vp, _i, _i, _i]),
     "plipmi_similarity_topk": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "plipmi_set_text_packing": (_i, [_vp, _i]),
     "plipmi_tower_shape": (_i, [_vp, _i, C.POINTER(C.c_int32)]),

@@ -27,6 +27,7 @@
 #include "gemm.h"
 #include "kernels.h"
 #include "probe_solver.h"
+#include "resize_ragged.h"
 
 #ifndef PLIPMI_DEFAULT_ATTENTION
 #define PLIPMI_DEFAULT_ATTENTION 1
@@ -1213,6 +1214,36 @@ int plipmi_resize_crop_u8(plipmi_handle h, const uint8_t* src, int B, int H, int
   return PLIPMI_OK;
 }
 
+size_t plipmi_resize_ragged_workspace(const int32_t* hw_host, int B, int n_px, int ksize) {
+  if (!hw_host || B <= 0 || n_px <= 0 || ksize <= 0) return 0;
+  return rr_layout(hw_host, B, n_px, ksize).total;
+}
+
+int plipmi_resize_crop_u8_ragged(plipmi_handle h, const uint8_t* src, size_t src_bytes, const int64_t* offsets, const int32_t* hw,
+                                 const int64_t* offsets_host, const int32_t* hw_host, int B, int n_px, int crop_rule, int ksize,
+                                 void* workspace, size_t workspace_bytes, uint8_t* dst, void* stream) {
+  if (!h || B < 0 || n_px <= 0 || (crop_rule != 0 && crop_rule != 1)) return fail(PLIPMI_ERR_INVALID, "bad argument");
+  if (B == 0) return PLIPMI_OK;
+  if (B > kRaggedMaxBatch) return fail(PLIPMI_ERR_INVALID, "%d images in one call (at most %d)", B, kRaggedMaxBatch);
+  if (!src || !offsets || !hw || !offsets_host || !hw_host || !workspace || !dst)
+    return fail(PLIPMI_ERR_INVALID, "null src/offsets/hw/workspace/dst");
+  int need = 0, max_cap = 0;
+  const char* why = "";
+  if (const int bad = rr_check_batch(offsets_host, hw_host, B, n_px, crop_rule, src_bytes, &need, &max_cap, &why))
+    return fail(PLIPMI_ERR_INVALID, "image %d (%d x %d at byte %lld of %zu): %s", bad - 1, hw_host[2 * (bad - 1)],
+                hw_host[2 * (bad - 1) + 1], (long long)offsets_host[bad - 1], src_bytes, why);
+  if (ksize < need) return fail(PLIPMI_ERR_INVALID, "ksize %d is below the %d taps of the batch's largest scale", ksize, need);
+  const RaggedLayout L = rr_layout(hw_host, B, n_px, ksize);
+  if (workspace_bytes < L.total)
+    return fail(PLIPMI_ERR_INVALID, "workspace of %zu bytes, plipmi_resize_ragged_workspace asks for %zu", workspace_bytes, L.total);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  double bytes = (double)B * n_px * n_px * 3;
+  for (int b = 0; b < B; ++b) bytes += (double)hw_host[2 * b] * hw_host[2 * b + 1] * 3;
+  Scope sc(h, s, "resize_crop_u8_ragged", 0, bytes + 2.0 * (double)L.tmp_bytes);
+  HIP_TRY(launch_resize_crop_ragged(src, src_bytes, offsets, hw, B, n_px, crop_rule, ksize, max_cap, workspace, L, dst, s));
+  return PLIPMI_OK;
+}
+
 int plipmi_similarity_topk(plipmi_handle h, const float* keys, int Nq, const float* space, int Ns, int D, int k,
                            int64_t* idx, float* vals, void* stream) {
   if (!h || Nq < 0 || Ns <= 0 || D <= 0) return fail(PLIPMI_ERR_INVALID, "bad argument");
@@ -1495,6 +1526,18 @@ int plipmi_resample_pos(const float* src, float* dst, int n0, int gh, int gw, in
   if (!src || !dst || src == dst || n0 <= 0 || gh <= 0 || gw <= 0 || D <= 0 || 1 + gh * gw > 1024 * 1024)
     return fail(PLIPMI_ERR_INVALID, "bad argument (src [1 + n0*n0, D], dst [1 + gh*gw, D], distinct)");
   HIP_TRY(launch_resample_pos(src, dst, n0, gh, gw, D, reinterpret_cast<hipStream_t>(stream)));
+  return PLIPMI_OK;
+}
+int plipmi_resize_ragged_tables(int in_size, int out_size, int first, int count, int ksize, int32_t* bounds, int32_t* coef,
+                                void* stream) {
+  if (in_size < 1 || out_size < 1 || first < 0 || count < 0 || first + count > out_size)
+    return fail(PLIPMI_ERR_INVALID, "bad argument (outputs first .. first + count of out_size)");
+  if ((double)in_size / (double)out_size > (double)kRaggedMaxRatio || ksize < rr_ksize(in_size, out_size))
+    return fail(PLIPMI_ERR_INVALID, "in / out above %d, or ksize %d below the axis's %d taps", kRaggedMaxRatio, ksize,
+                rr_ksize(in_size, out_size));
+  if (count == 0) return PLIPMI_OK;
+  if (!bounds || !coef) return fail(PLIPMI_ERR_INVALID, "null bounds/coef");
+  HIP_TRY(launch_ragged_tables(in_size, out_size, first, count, ksize, bounds, coef, reinterpret_cast<hipStream_t>(stream)));
   return PLIPMI_OK;
 }
 int plipmi_check_async(plipmi_handle h) {

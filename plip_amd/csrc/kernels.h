@@ -98,6 +98,16 @@ hipError_t launch_resize_crop_u8(const uint8_t* src, int B, int H, int W, int n,
                                  int left, const int* yb, const int* yk, int yks, int top, int r0, int R,
                                  uint8_t* tmp, uint8_t* dst, hipStream_t s);
 
+// The same resize + crop for a RAGGED batch (resize_ragged.hip): B images of their own sizes packed in src at offsets[b] (device int64),
+// hw int32 [B, 2] on the device; geometry, coefficient tables and the layout of the intermediate are computed on the device inside
+// `workspace` (resize_ragged.h RaggedLayout L, sized and checked by the caller on the host).  dst [B, n, n, 3].
+struct RaggedLayout;
+hipError_t launch_resize_crop_ragged(const uint8_t* src, size_t src_bytes, const int64_t* offsets, const int32_t* hw, int B, int n,
+                                     int rule, int ks, int max_cap, void* workspace, const RaggedLayout& L, uint8_t* dst,
+                                     hipStream_t s);
+// its table kernel alone, one axis: outputs first .. first + count of `in` -> `out` pixels; bounds int32 [count, 2], coef int32 [count, ks]
+hipError_t launch_ragged_tables(int in, int out, int first, int count, int ks, int* bounds, int* coef, hipStream_t s);
+
 // dst[r, 0:cols] = (T)(scale * src[r, 0:cols]), dst[r, cols:dst_ld] = 0   (weight packing)
 hipError_t launch_convert(const float* src, void* dst, int dst_dtype, int rows, int cols, int dst_ld, float scale,
                           hipStream_t s);

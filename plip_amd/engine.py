@@ -47,6 +47,35 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def ragged_blob(images, out: Optional[torch.Tensor] = None):
+    """Images of differing sizes -> ``(blob, offsets, hw)`` for :meth:`Engine.resize_crop_ragged`: ``blob`` = 1-D uint8 tensor holding
+    the descriptors the kernels read (offsets int64 [B], then hw int32 [B,2]) followed by the images' RGB bytes end to end
+    (``preprocess.pack_ragged``), so that ONE host-to-device copy carries a batch; ``offsets`` / ``hw`` are the host copies the C entry
+    validates.  ``out``: a 1-D uint8 tensor to pack into (a pinned staging buffer of at least :func:`ragged_blob_bytes` bytes)."""
+    from .preprocess import _as_rgb_u8, pack_ragged
+    arrs = [_as_rgb_u8(im) for im in images]
+    head = 16 * len(arrs)
+    total = head + sum(a.size for a in arrs)
+    if out is None:
+        out = torch.empty((total,), dtype=torch.uint8)
+    elif out.numel() < total:
+        raise ValueError(f"ragged_blob: the buffer holds {out.numel()} bytes, the batch needs {total}")
+    view = out.numpy()
+    _, offsets, hw = pack_ragged(arrs, out=view[head:total])
+    view[:head // 2].view(np.int64)[:] = offsets
+    view[head // 2:head].view(np.int32)[:] = hw.reshape(-1)
+    return out[:total], offsets, hw
+
+
+def ragged_blob_bytes(images) -> int:
+    """Bytes :func:`ragged_blob` needs for these images (arrays / PIL images; nothing is decoded or converted)."""
+    total = 16 * len(images)
+    for im in images:
+        h, w = (im.shape[0], im.shape[1]) if isinstance(im, np.ndarray) else (im.size[1], im.size[0])
+        total += h * w * 3
+    return total
+
+
 class Engine:
     """One MI355X engine = packed weights + workspace for ``max_batch`` images/captions."""
 
@@ -153,7 +182,7 @@ class Engine:
         batch per tower at a time, two engines on two streams run consecutive batches of a corpus side by side (``lanes``)."""
         other = object.__new__(Engine)
         other.__dict__.update({k: v for k, v in self.__dict__.items()
-                               if k not in ("_h", "_lanes", "_vis", "pair_stream_ratio", "_resolutions", "_resize_plans")})
+                               if k not in ("_h", "_lanes", "_vis", "pair_stream_ratio", "_resolutions", "_resize_plans", "_ragged_ws")})
         other._h = C.c_void_p()
         other._lanes, other._no_lanes, other.use_lanes = None, 0, False        # a clone is a lane, it does not fan out itself
         with torch.cuda.device(self.device):
@@ -199,7 +228,7 @@ class Engine:
         mb = max(1, (self.max_batch * self.v_tokens) // tokens) if tokens else 1
         other = object.__new__(Engine)
         other.__dict__.update({k: v for k, v in self.__dict__.items()
-                               if k not in ("_h", "_lanes", "_vis", "pair_stream_ratio", "_resolutions", "_resize_plans")})
+                               if k not in ("_h", "_lanes", "_vis", "pair_stream_ratio", "_resolutions", "_resize_plans", "_ragged_ws")})
         other._h = C.c_void_p()
         other._lanes, other._no_lanes = None, 0
         with torch.cuda.device(self.device):
@@ -545,6 +574,46 @@ class Engine:
                 0 if plan["xk"] is None else plan["xk"].shape[1], plan["left"], _ptr(dev["yb"]), _ptr(dev["yk"]),
                 0 if plan["yk"] is None else plan["yk"].shape[1], plan["top"], r0, R, _ptr(tmp), _ptr(dst),
                 self._stream()), "plipmi_resize_crop_u8")
+        return dst
+
+    def resize_crop_ragged(self, images, crop: str = "torchvision", n_px: Optional[int] = None) -> torch.Tensor:
+        """uint8 RGB images of DIFFERING sizes -> uint8 [B,n,n,3] tiles on the device, each bit-identical to Pillow's bicubic resize
+        (shortest edge -> n) + centre crop of that image; feed the result to :meth:`encode_image_u8`.  ``images``: a list of arrays /
+        PIL images (packed here, one pageable H2D copy), or a :func:`ragged_blob` result ``(blob, offsets, hw)`` whose blob may sit in
+        pinned memory or already on the device.  One copy carries the pixels and their descriptors; geometry and coefficient tables are
+        computed on the device (include/plipmi.h ``plipmi_resize_crop_u8_ragged``), in a workspace this engine keeps and grows.
+        Everything is enqueued on the current stream, nothing synchronises.  ``n_px``: the tile size (default: the engine's)."""
+        from .preprocess import ragged_ksize
+        if crop not in ("torchvision", "hf"):
+            raise ValueError(f"unknown crop rule {crop!r} (expected 'hf' or 'torchvision')")
+        if n_px is None:
+            n_px, n_w = self.image_hw
+            if n_px != n_w:
+                raise ValueError(f"resize_crop_ragged makes square tiles; this engine takes {n_px} x {n_w} images")
+        n = int(n_px)
+        blob, offsets, hw = images if isinstance(images, tuple) else ragged_blob(images)
+        B = int(hw.shape[0])
+        if B == 0:
+            return torch.empty((0, n, n, 3), dtype=torch.uint8, device=self.device)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        hw = np.ascontiguousarray(hw, dtype=np.int32).reshape(B, 2)
+        if blob.dtype != torch.uint8 or blob.dim() != 1 or blob.numel() < 16 * B:
+            raise ValueError("the packed batch is a 1-D uint8 tensor: descriptors (16 bytes per image) then pixels")
+        ks = ragged_ksize(hw, n)
+        with torch.cuda.device(self.device):
+            need = int(self.lib.plipmi_resize_ragged_workspace(hw.ctypes.data_as(C.c_void_p), B, n, ks))
+            ws = self.__dict__.get("_ragged_ws")
+            if ws is None or ws.numel() < need:
+                if ws is not None:
+                    ws.record_stream(torch.cuda.current_stream(self.device))      # its last kernels may still be running there
+                ws = self._ragged_ws = torch.empty((max(need, 1) * 5 // 4,), dtype=torch.uint8, device=self.device)
+            src = blob.to(self.device, non_blocking=True)
+            dst = torch.empty((B, n, n, 3), dtype=torch.uint8, device=self.device)
+            base = src.data_ptr()
+            _lib.check(self.lib.plipmi_resize_crop_u8_ragged(
+                self._h, C.c_void_p(base + 16 * B), src.numel() - 16 * B, C.c_void_p(base), C.c_void_p(base + 8 * B),
+                offsets.ctypes.data_as(C.c_void_p), hw.ctypes.data_as(C.c_void_p), B, n, 1 if crop == "hf" else 0, ks,
+                _ptr(ws), ws.numel(), _ptr(dst), self._stream()), "plipmi_resize_crop_u8_ragged")
         return dst
 
     def similarity_topk(self, keys: torch.Tensor, space: torch.Tensor, k: int, return_values: bool = False):

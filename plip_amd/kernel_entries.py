@@ -7,6 +7,7 @@ GPU tests can compare them with fp64 references, plus the host mirrors of the sp
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -390,3 +391,22 @@ def head_gemm(a: torch.Tensor, w: torch.Tensor, scale: float = 1.0) -> torch.Ten
     with torch.cuda.device(a.device):
         _lib.check(lib.plipmi_head_gemm(_ptr(a), _ptr(w), _ptr(out), M, N, K, float(scale), _stream(a)), "plipmi_head_gemm")
     return out
+
+
+def resize_ragged_tables(in_size: int, out_size: int, first: int = 0, count: Optional[int] = None, ksize: Optional[int] = None,
+                         device="cuda"):
+    """``plipmi_resize_ragged_tables``: the table kernel of the ragged resize alone, one axis resampled from ``in_size`` to
+    ``out_size`` pixels, outputs ``first .. first + count`` (default: all) -> (bounds int32 [count, 2], coef int32 [count, ksize]) on
+    the device, to compare with ``preprocess.resample_coeffs(in_size, out_size)`` rows ``first .. first + count``."""
+    lib = _lib.load()
+    count = out_size - first if count is None else int(count)
+    if ksize is None:
+        scale = float(torch.tensor(in_size, dtype=torch.float32)) / out_size
+        ksize = int(math.ceil(2.0 * max(scale, 1.0))) * 2 + 1
+    dev = torch.device(device)
+    bounds = torch.zeros((count, 2), dtype=torch.int32, device=dev)
+    coef = torch.zeros((count, int(ksize)), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.plipmi_resize_ragged_tables(int(in_size), int(out_size), int(first), count, int(ksize), _ptr(bounds), _ptr(coef),
+                                                   _stream(bounds)), "plipmi_resize_ragged_tables")
+    return bounds, coef

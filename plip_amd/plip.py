@@ -85,6 +85,130 @@ def _uniform_u8_images(chunk, n_px):
     return np.stack(arrs)
 
 
+# ---- ragged batches (``ragged_resize=True``): images of differing sizes resized on the GPU (Engine.resize_crop_ragged) -------------
+def _u8_image_hw(im):
+    """(h, w) of a uint8 array (grey, RGB, RGBA) or PIL image -- what ``preprocess.pack_ragged`` takes --, else None."""
+    if isinstance(im, np.ndarray):
+        ok = im.dtype == np.uint8 and (im.ndim == 2 or (im.ndim == 3 and im.shape[2] in (3, 4)))
+        return (int(im.shape[0]), int(im.shape[1])) if ok else None
+    if isinstance(im, str) or torch.is_tensor(im) or not (hasattr(im, "size") and hasattr(im, "mode")):
+        return None
+    return int(im.size[1]), int(im.size[0])
+
+
+def _ragged_segments(chunk, n_px):
+    """A list of images -> ``[("ragged", [images...]) | ("host", [image]), ...]`` in order: runs of images the device entry takes, and
+    one "host" entry per image it does not (a float array, an in / out ratio over the limit), which keeps the Pillow path.  None
+    when the chunk is not a list or holds nothing for the device."""
+    from .preprocess import ragged_supported
+    if not isinstance(chunk, (list, tuple)) or len(chunk) == 0:
+        return None
+    segs = []
+    for im in chunk:
+        hw = _u8_image_hw(im)
+        if hw is not None and ragged_supported(hw[0], hw[1], n_px):
+            if segs and segs[-1][0] == "ragged":
+                segs[-1][1].append(im)
+            else:
+                segs.append(("ragged", [im]))
+        else:
+            segs.append(("host", [im]))
+    return segs if any(k == "ragged" for k, _ in segs) else None
+
+
+def _encode_segments(e, segs, n_px, crop, normalize=False):
+    """The segments of one chunk on engine ``e`` (inside a lane: every device-side step, the copy included, is enqueued here)."""
+    outs = []
+    for kind, items in segs:
+        if kind == "ragged":
+            outs.append(e.encode_image_u8(e.resize_crop_ragged(items, crop=crop), normalize=normalize))
+        else:
+            outs.append(e.encode_image(torch.from_numpy(preprocess_images(items, n_px, crop=crop)), normalize=normalize))
+    return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+
+class _PinnedPair:
+    """Two page-locked byte buffers used alternately by the batch producer of ``pipeline.run_batches``: batch k + 1 is packed into
+    one while the copy of batch k leaves the other (``run_batches`` waits for that copy before the producer runs again)."""
+
+    def __init__(self):
+        self.bufs, self.k = [None, None], 0
+
+    def take(self, nbytes: int) -> torch.Tensor:
+        i, self.k = self.k, self.k ^ 1
+        if self.bufs[i] is None or self.bufs[i].numel() < nbytes:
+            self.bufs[i] = torch.empty((max(nbytes, 1) * 5 // 4,), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        return self.bufs[i]
+
+
+def _decode_image(im):
+    if isinstance(im, str):            # paths are opened where this runs, i.e. on the worker threads
+        from PIL import Image
+        im = Image.open(im)
+        im.load()
+    return im
+
+
+def _ragged_prepare(chunk, n_px, crop, pool, pinned):
+    """One decoded batch -> ``(("ragged", offsets, hw, rows, host), blob)`` for ``run_batches``: the images the device takes, converted
+    to RGB on the workers and packed with their descriptors into a pinned buffer; ``rows`` = their positions in the batch (None: all of
+    it) and ``host`` = [(position, fp32 pixels)] of the others, preprocessed on the host.  None: nothing here for the device."""
+    from .engine import ragged_blob
+    from .preprocess import _as_rgb_u8, preprocess_image
+    segs = _ragged_segments(chunk, n_px)
+    if segs is None:
+        return None
+    flags = [k == "ragged" for k, items in segs for _ in items]
+    dev = [im for im, f in zip(chunk, flags) if f]
+    rgb = list(pool.map(_as_rgb_u8, dev)) if pool is not None else [_as_rgb_u8(im) for im in dev]
+    out = pinned.take(16 * len(rgb) + sum(a.size for a in rgb)) if pinned is not None else None
+    blob, offsets, hw = ragged_blob(rgb, out=out)
+    host = [(i, preprocess_image(chunk[i], n_px, crop)) for i, f in enumerate(flags) if not f]
+    rows = None if not host else [i for i, f in enumerate(flags) if f]
+    return ("ragged", offsets, hw, rows, host), blob
+
+
+def _ragged_consume(e, tag, blob, crop, normalize=False):
+    _, offsets, hw, rows, host = tag
+    u = e.encode_image_u8(e.resize_crop_ragged((blob, offsets, hw), crop=crop), normalize=normalize)
+    if not host:
+        return u
+    out = torch.empty((len(rows) + len(host), u.shape[1]), dtype=u.dtype, device=u.device)
+    out[torch.as_tensor(rows, device=u.device)] = u
+    for i, px in host:
+        out[i:i + 1] = e.encode_image(torch.from_numpy(px[None]), normalize=normalize).to(u.device)
+    return out
+
+
+def prepare_routed_batch(chunk, n_px, crop, pool=None, pinned=None, ragged=True):
+    """Decode and route one batch of images the way ``PLIP.encode_images`` does: ``("tiles", uint8 [B,n,n,3])`` already at the model
+    resolution, ``("resize", uint8 [B,H,W,3])`` one size, ``(("ragged", ...), blob)`` differing sizes (``ragged``), else
+    ``("pixels", fp32 [B,3,n,n])`` from the host's Pillow path.  ``consume_routed_batch`` runs the result on an engine."""
+    from .preprocess import preprocess_image
+    chunk = list(pool.map(_decode_image, chunk)) if pool is not None else [_decode_image(c) for c in chunk]
+    tiles = _native_u8_tiles(chunk, n_px)
+    if tiles is not None:
+        return "tiles", tiles
+    same = _uniform_u8_images(chunk, n_px)
+    if same is not None:
+        return "resize", same
+    rb = _ragged_prepare(chunk, n_px, crop, pool, pinned) if ragged else None
+    if rb is not None:
+        return rb
+    one = lambda im: preprocess_image(im, n_px, crop)
+    return "pixels", np.stack(list(pool.map(one, chunk)) if pool is not None else [one(c) for c in chunk])
+
+
+def consume_routed_batch(e, tag, t, crop, normalize=False):
+    if isinstance(tag, tuple):
+        return _ragged_consume(e, tag, t, crop, normalize)
+    if tag == "tiles":
+        return e.encode_image_u8(t, normalize=normalize)
+    if tag == "resize":
+        return e.encode_image_u8(e.resize_crop_u8(t, crop=crop), normalize=normalize)
+    return e.encode_image(t, normalize=normalize)
+
+
 @contextlib.contextmanager
 def _lane_loop(eng):
     """``Engine.lane_loop`` where the engine has one (a PlipModel's); any other engine object: every call on it, in order."""
@@ -98,11 +222,12 @@ def _lane_loop(eng):
 
 class PLIP:
     coalesce = True          # engine calls carry up to engine.max_batch rows whatever ``batch_size`` says (module docstring)
+    ragged_resize = False    # lists of differing image sizes: host Pillow (False) or the GPU's ragged resize (constructor keyword)
 
     def __init__(self, model_name: str = None, auth_token=None, *, model: Optional[PlipModel] = None,
                  tokenizer: Optional[Callable] = None, tokenizer_dir: Optional[str] = None, dtype: str = "bf16",
                  max_batch: int = 256, device: str = "cuda:0", pack_captions: bool = False, text_f16: bool = False,
-                 text_f16_layers: Optional[int] = None):
+                 text_f16_layers: Optional[int] = None, ragged_resize: bool = False):
         """``model_name``: local HF directory (what ``CLIPModel/CLIPProcessor.from_pretrained`` take, plip.py:26-27)
         or an OpenAI-clip ``.pt`` state dict.  The tokenizer comes from ``tokenizer`` (a callable), else from
         ``tokenizer_dir`` / the model directory when it holds ``vocab.json`` + ``merges.txt``; with neither,
@@ -112,7 +237,10 @@ class PLIP:
         ``text_f16`` (bf16 engine): the text tower on IEEE-half operands (PLIPMI_FLAG_TEXT_TOWER_F16); ``text_f16_layers``
         (bf16 engine): only that many leading text blocks (plipmi_config.text_f16_layers; None = the default).  The engine's other
         per-handle options (ln_fold, pooled_last_block, mfma_attention, graph_batch) are reached by building the model
-        explicitly -- ``PLIP(model=PlipModel.from_pretrained(path, **engine_options))``."""
+        explicitly -- ``PLIP(model=PlipModel.from_pretrained(path, **engine_options))``.  ``ragged_resize`` (extension): a batch of
+        uint8 / PIL images whose sizes DIFFER is resized and cropped on the GPU too (``Engine.resize_crop_ragged``, Pillow-exact)
+        instead of image by image in host Pillow; batches of one size and native tiles keep their routes, float inputs and images
+        shrunk more than 64 x keep the host path.  Off: every route is as before."""
         if not torch.cuda.is_available():
             raise RuntimeError("plip_amd.PLIP needs an MI355X (ROCm) GPU; there is no CPU path")
         self.device = device
@@ -133,6 +261,7 @@ class PLIP:
         if pack_captions:
             self.model.engine.set_text_packing(True)
         self.tokenizer = tokenizer
+        self.ragged_resize = bool(ragged_resize)
         self.model_hash = hash            # the reference returns the builtin too (plip.py:29)
         self.image_vectors = None
 
@@ -158,6 +287,8 @@ class PLIP:
             if kind == "stage":            # native tiles: each copied ONCE, into the pinned staging rows; one H2D, one engine call
                 stage = self._fill_stage(pend, n_px, cap)       # (the H2D copy inside the call is synchronous: the rows may be refilled)
                 outs.append(run(lambda e: e.encode_image_u8(stage)))
+            elif kind == "ragged":         # images of differing sizes: packed, copied, resized and encoded inside the lane's call
+                outs.append(run(lambda e, imgs=pend: e.encode_image_u8(e.resize_crop_ragged(imgs, crop=_CROP))))
             elif pend:
                 if len(pend) > 1 and any(t.is_cuda for t in pend):
                     pend = [t.to(eng.device) for t in pend]
@@ -185,6 +316,17 @@ class PLIP:
                         continue
                 tiles = _native_u8_tiles(chunk, n_px)
                 same = _uniform_u8_images(chunk, n_px) if tiles is None else None
+                segs = _ragged_segments(chunk, n_px) if (self.ragged_resize and tiles is None and same is None) else None
+                if segs is not None:       # differing sizes (ragged_resize): the GPU resizes them as well
+                    if len(segs) == 1:     # nothing for the host in this chunk: coalesced like the other routes
+                        if kind is not None and (kind != "ragged" or rows + len(chunk) > cap):
+                            flush()
+                        pend.extend(segs[0][1])
+                        kind, rows = "ragged", rows + len(chunk)
+                    else:                  # some images keep the host path: the chunk's segments in order, in one lane call
+                        flush()
+                        outs.append(run(lambda e, segs=segs: _encode_segments(e, segs, n_px, _CROP)))
+                    continue
                 if tiles is not None:      # already n_px x n_px uint8: normalise on the GPU, fused into the unfold
                     k, t = "tiles", torch.from_numpy(tiles)
                 elif same is not None:     # one size, not the model's: Pillow-exact resize + crop on the GPU as well
@@ -258,6 +400,11 @@ class PLIP:
                     chunk = [Image.open(c) if isinstance(c, str) else c for c in chunk]
                 tiles = _native_u8_tiles(chunk, n_px)
                 same = _uniform_u8_images(chunk, n_px) if tiles is None else None
+                segs = _ragged_segments(chunk, n_px) if (self.ragged_resize and tiles is None and same is None) else None
+                if segs is not None:       # differing sizes (ragged_resize): one lane call per chunk, every device-side step inside it
+                    flush()
+                    outs.append(run(lambda e, segs=segs: _encode_segments(e, segs, n_px, _CROP)))
+                    continue
                 if tiles is not None:
                     k, h = "tiles", tiles
                 elif same is not None:
@@ -305,17 +452,24 @@ class PLIP:
             same = _uniform_u8_images(chunk, n_px)
             if same is not None:
                 return "resize", same
+            if self.ragged_resize:         # differing sizes: the workers only decode and convert; packed into the pinned double buffer
+                rb = _ragged_prepare(chunk, n_px, _CROP, pool, pinned)
+                if rb is not None:
+                    return rb
             one = lambda im: preprocess_image(im, n_px, _CROP)
             arrs = list(pool.map(one, chunk)) if pool is not None else [one(c) for c in chunk]
             return "pixels", np.stack(arrs)
 
         def consume(tag, t, e=eng):
+            if isinstance(tag, tuple):     # ("ragged", ...): resized on the engine (and in the stream) the batch runs on
+                return _ragged_consume(e, tag, t, _CROP)
             if tag == "tiles":
                 return e.encode_image_u8(t)
             if tag == "resize":
                 return e.encode_image_u8(e.resize_crop_u8(t, crop=_CROP))
             return e.encode_image(t, normalize=False)
 
+        pinned = _PinnedPair()
         bs = min(int(batch_size), eng.max_batch)
         lanes = eng.lanes() if getattr(eng, "use_lanes", False) and hasattr(eng, "lanes") else None
         with torch.no_grad():

@@ -138,6 +138,82 @@ def resize_crop_reference(img_u8: np.ndarray, plan) -> np.ndarray:
     return out.astype(np.uint8)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# Ragged batches (plipmi_resize_crop_u8_ragged): images of differing sizes packed end to end, geometry and coefficient
+# tables computed on the device.  The host only packs bytes and sizes buffers; the functions below are that packing, the
+# limits the C entry checks, and the CPU oracle of the whole call.
+# ---------------------------------------------------------------------------------------------------------------
+RAGGED_MAX_RATIO = 64          # largest in / out ratio of an axis the device entry takes (csrc/resize_ragged.h)
+
+
+def _as_rgb_u8(img) -> np.ndarray:
+    """array or PIL image -> uint8 [h, w, 3]; anything that is not RGB uint8 goes through ``.convert("RGB")``, as the
+    reference's datasets do (reproducibility/dataset_loading/internal_datasets.py:42)."""
+    if isinstance(img, np.ndarray) and img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3:
+        return img
+    if isinstance(img, np.ndarray):
+        if img.dtype != np.uint8:
+            raise TypeError(f"pack_ragged takes uint8 arrays or PIL images, got an array of {img.dtype}")
+        from PIL import Image
+        img = Image.fromarray(img)
+    return np.asarray(img.convert("RGB"), dtype=np.uint8)
+
+
+def resize_output_size(h: int, w: int, n_px: int):
+    """(nh, nw) of torchvision ``Resize(n_px)``: shortest edge -> n_px, long edge ``int(n_px * long / short)``."""
+    return (int(n_px * h / w), n_px) if w <= h else (n_px, int(n_px * w / h))
+
+
+def ragged_supported(h: int, w: int, n_px: int) -> bool:
+    """Whether the device entry takes an h x w image: both sides at least 1 and no in / out ratio above RAGGED_MAX_RATIO."""
+    if h < 1 or w < 1:
+        return False
+    nh, nw = resize_output_size(h, w, n_px)
+    return h / nh <= RAGGED_MAX_RATIO and w / nw <= RAGGED_MAX_RATIO
+
+
+def ragged_ksize(hw, n_px: int) -> int:
+    """Taps per coefficient row for a batch of sizes ``hw`` [B, 2] = (h, w): ``2 * ceil(2 * max(scale, 1)) + 1`` at the batch's
+    largest per-axis scale -- the row width ``resample_coeffs`` gives that axis."""
+    hw = np.asarray(hw, dtype=np.int64).reshape(-1, 2)
+    if hw.shape[0] == 0 or int(hw.min()) < 1:       # (a side below 1 is refused by the C entry whatever the row width)
+        return 5
+    h, w = hw[:, 0], hw[:, 1]
+    tall = w <= h
+    nh = np.where(tall, (n_px * h / w).astype(np.int64), n_px)          # int(n_px * long / short): true division, truncated
+    nw = np.where(tall, n_px, (n_px * w / h).astype(np.int64))
+    scale = np.concatenate([h.astype(np.float32).astype(np.float64) / nh, w.astype(np.float32).astype(np.float64) / nw])
+    return int(np.ceil(2.0 * max(float(scale.max()), 1.0))) * 2 + 1
+
+
+def pack_ragged(images: Sequence, out: "np.ndarray | None" = None):
+    """Arrays / PIL images of any sizes -> ``(buf uint8 [sum h*w*3], offsets int64 [B], hw int32 [B, 2])``: the images' RGB bytes
+    end to end, image b at ``buf[offsets[b]:]`` with ``hw[b] = (h, w)``.  ``out``: a uint8 buffer to pack into (a pinned staging
+    buffer); ``buf`` is then its leading slice."""
+    arrs = [_as_rgb_u8(im) for im in images]
+    hw = np.asarray([a.shape[:2] for a in arrs], dtype=np.int32).reshape(len(arrs), 2)
+    sizes = hw[:, 0].astype(np.int64) * hw[:, 1] * 3
+    offsets = np.zeros(len(arrs), np.int64)
+    if len(arrs) > 1:
+        np.cumsum(sizes[:-1], out=offsets[1:])
+    total = int(sizes.sum())
+    buf = np.empty(total, np.uint8) if out is None else out[:total]
+    if buf.shape[0] != total:
+        raise ValueError(f"pack_ragged: the output buffer holds {0 if out is None else out.shape[0]} bytes, the images need {total}")
+    for a, o, sz in zip(arrs, offsets.tolist(), sizes.tolist()):
+        buf[o:o + sz] = a.reshape(-1)
+    return buf, offsets, hw
+
+
+def resize_crop_ragged_reference(images: Sequence, n_px: int = 224, crop: str = "torchvision") -> np.ndarray:
+    """CPU oracle of the ragged entry: :func:`resize_crop_reference` per image -> uint8 [B, n_px, n_px, 3]."""
+    out = np.zeros((len(images), n_px, n_px, 3), np.uint8)
+    for i, im in enumerate(images):
+        a = _as_rgb_u8(im)
+        out[i] = resize_crop_reference(a, resize_crop_plan(a.shape[1], a.shape[0], n_px, crop))
+    return out
+
+
 def preprocess_images(images: Sequence, n_px: int = 224, crop: str = "torchvision") -> np.ndarray:
     return np.stack([preprocess_image(i, n_px, crop) for i in images]) if len(images) else \
         np.zeros((0, 3, n_px, n_px), np.float32)

@@ -21,9 +21,16 @@ from . import cacher
 
 
 class CLIPEmbedder:
+    ragged_resize = False
+
     def __init__(self, model: PlipModel, preprocess: Optional[Callable] = None, name: str = "plip",
-                 backbone: str = "", tokenizer: Optional[Callable] = None):
+                 backbone: str = "", tokenizer: Optional[Callable] = None, ragged_resize: bool = False):
+        """``ragged_resize`` (extension, only without a ``preprocess`` of the caller's): images are not preprocessed one by one in
+        host Pillow -- uint8 / PIL batches are resized, cropped (torchvision's rule, as ``_transform`` does) and normalised on the GPU,
+        whatever their sizes (``plip.prepare_routed_batch``: native tiles / one size / differing sizes; float inputs and images
+        shrunk more than 64 x keep the host path).  Off: every image goes through ``preprocess`` as before."""
         self.model = model
+        self.ragged_resize = bool(ragged_resize) and preprocess is None
         self.preprocess = preprocess if preprocess is not None else \
             (lambda img: preprocess_image(img, model.config.image_size))
         self.name = name
@@ -57,6 +64,8 @@ class CLIPEmbedder:
     @torch.no_grad()
     def embed_images(self, list_of_images, device="cuda", num_workers=1, batch_size=32) -> np.ndarray:
         eng = self.model.engine
+        if self.ragged_resize and not torch.is_tensor(list_of_images) and not isinstance(list_of_images, np.ndarray):
+            return self._embed_images_routed(list(list_of_images), num_workers, batch_size)
         if num_workers and num_workers > 1 and not torch.is_tensor(list_of_images) and not (
                 isinstance(list_of_images, np.ndarray) and list_of_images.dtype != object and list_of_images.ndim == 4):
             from ..pipeline import run_batches          # decode on a thread pool, H2D on a copy stream
@@ -78,6 +87,30 @@ class CLIPEmbedder:
                 out.append(run(lambda e, px=px: e.encode_image(px, normalize=True)))       # :48 encode_image + :53 row normalisation
         if not out:
             return np.zeros((0, self.model.config.projection_dim), np.float32)
+        return torch.cat(out).cpu().numpy()
+
+    def _embed_images_routed(self, images: list, num_workers, batch_size) -> np.ndarray:
+        """``ragged_resize``: every batch is decoded and routed on the host (``plip.prepare_routed_batch``) and resized, cropped,
+        normalised and encoded on the GPU, inside the lane it runs on; with ``num_workers > 1`` one batch ahead on a thread pool."""
+        from ..plip import _PinnedPair, consume_routed_batch, prepare_routed_batch
+        eng, n_px, crop = self.model.engine, self.model.config.image_size, "torchvision"
+        if not images:
+            return np.zeros((0, self.model.config.projection_dim), np.float32)
+        if num_workers and num_workers > 1:
+            from ..pipeline import run_batches
+            pinned = _PinnedPair()
+            step = max(1, min(int(batch_size), eng.max_batch))
+            outs = run_batches(images, step, None, lambda tag, t, e=eng: consume_routed_batch(e, tag, t, crop, normalize=True),
+                               device=eng.device, num_workers=num_workers,
+                               prepare_batch=lambda chunk, pool: prepare_routed_batch(chunk, n_px, crop, pool, pinned),
+                               lanes=eng.lanes() if eng.use_lanes else None)
+            return torch.cat(outs).cpu().numpy()
+        out = []
+        with eng.lane_loop() as run:
+            for a, b in self._chunks(len(images), batch_size):
+                tag, arr = prepare_routed_batch(images[a:b], n_px, crop)
+                t = arr if torch.is_tensor(arr) else torch.from_numpy(arr)
+                out.append(run(lambda e, tag=tag, t=t: consume_routed_batch(e, tag, t, crop, normalize=True)))
         return torch.cat(out).cpu().numpy()
 
     def _tokenize(self, captions):
