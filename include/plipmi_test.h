@@ -154,6 +154,38 @@ int plipmi_head_gemm(const float* A, const float* W, float* C, int M, int N, int
 int plipmi_resize_ragged_tables(int in_size, int out_size, int first, int count, int ksize, int32_t* bounds, int32_t* coef,
                                 void* stream);
 
+/* Kernel-level entries of the vision front end (csrc/towers.hip vision_embed) and of the two mechanisms the packed-caption path rests on,
+ * for tests/test_gpu_front_end.py.  As above: arguments checked on the host (PLIPMI_ERR_INVALID before any launch), then the engine's own
+ * launcher on `stream`; all pointers are device buffers; nothing synchronises. */
+
+/* The unfold pass: out [B * (H / patch) * (W / patch), Kpad] (dtype) = row (b, gi, gj), column (c, u, v) of the pixels, zeros in columns
+ * 3 * patch^2 .. Kpad.  from_u8 = 0: src fp32 NCHW [B, 3, H, W]; 1: src uint8 HWC tiles [B, H, W, 3], CLIP-normalised.  The grid floors.
+ * Kpad >= 3 * patch^2, Kpad % 4 == 0, src and out 16-byte aligned. */
+int plipmi_unfold_patches(int dtype, int from_u8, const void* src, void* out, int B, int H, int W, int patch, int Kpad, void* stream);
+/* x fp32 [B, tokens, D]: row 0 of every image = cls [D] + pos [D] (the position table's first row); the other rows are not touched.
+ * D % 4 == 0, tokens >= 1. */
+int plipmi_cls_rows(const float* cls, const float* pos, float* x, int B, int tokens, int D, void* stream);
+/* The patch GEMM (gemm.h EPI_PATCH): C fp32 [B * (np + 1), N], token row img * (np + 1) + 1 + p = A[img * np + p, :K] . W[n, :K] +
+ * pos[1 + p, n]; A [M = B * np, lda], W [N, ldw] (dtype), pos fp32 [np + 1, N].  CLS rows are not touched.  variant as plipmi_gemm_nt
+ * (-1 the cost model, 0 .. a tile, -2 the naive kernel).  M % np == 0, N % 4 == 0, lda / ldw >= K and multiples of 16 bytes. */
+int plipmi_gemm_patch(int dtype, int variant, int M, int N, int K, const void* A, int lda, const void* W, int ldw, const float* pos,
+                      int np, void* C, void* stream);
+/* The same rows from the patch GEMM with im2col on load (gemm.h ADDR 2 / 3, the ring tile), at ANY batch: exactly one of pixels (fp32
+ * NCHW [B, 3, H, W_px]) / tiles (uint8 HWC [B, H, W_px, 3]); W [N, 3 * patch^2] (dtype), pos fp32 [np + 1, N], C fp32 [B * (np + 1), N]
+ * with np = (H / patch) * (W_px / patch).  16-bit dtype, patch 16 or 32, W_px % 4 == 0, N % 256 == 0, every buffer below 4 GiB. */
+int plipmi_gemm_patch_gather(int dtype, const float* pixels, const uint8_t* tiles, const void* W, const float* pos, float* C, int B,
+                             int H, int W_px, int patch, int N, void* stream);
+/* plipmi_gemm_nt_ln with the live row count on the device (GemmParams.m_dev, the packed text tower): rows 0 .. min(*m_dev, M) - 1 are
+ * computed, M only sizes the grid, nothing past the live rows is written.  variant -1 or a tile (the naive and the small-M kernels do
+ * not read m_dev: -2 / -3 are refused). */
+int plipmi_gemm_nt_ln_rows(int dtype, int mode, int variant, int M, int N, int K, const void* A, const void* W, const float* bias,
+                           const float* stats, int ns, float eps, void* C, void* xb_out, float* st_out, const int32_t* m_dev,
+                           void* stream);
+/* plipmi_attention on packed rows: cu int32 [B + 1], caption b owns rows cu[b] .. cu[b + 1] - 1 of qkv / out (1 <= its length <= S);
+ * key_mask keeps its [B, S] layout.  impl 1 and S <= 128 only (the short-sequence MFMA kernel). */
+int plipmi_attention_packed(int dtype, int impl, const void* qkv, void* out, int B, int S, int H, int causal, const int64_t* key_mask,
+                            const int32_t* cu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

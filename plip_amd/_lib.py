@@ -83,6 +83,12 @@ TEST_SYMBOLS = {
     "plipmi_pool_gather": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "plipmi_head_gemm": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "plipmi_resize_ragged_tables": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "plipmi_unfold_patches": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "plipmi_cls_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "plipmi_gemm_patch": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "plipmi_gemm_patch_gather": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "plipmi_gemm_nt_ln_rows": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "plipmi_attention_packed": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 # every symbol include/plipmi.h declares (the product interface): (restype, argtypes)
 SYMBOLS = {

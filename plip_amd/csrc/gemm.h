@@ -35,6 +35,7 @@ namespace plipmi {
 
 // first-class vector (HIP's uint4 struct keeps staging arrays in scratch)
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 enum Epilogue : int {
   EPI_BIAS = 0,        // C(T)   = acc + bias[n]
@@ -1307,9 +1308,11 @@ void gemm_nt_kernel(const GemmParams p) {
                     make_float2(ssum, m2);
             }
           }
-          // (a band's second row may lie past the live rows while its first does not: its byte half then goes to the plane's padding)
-          if (m_first < Mrt)
-            store16(reinterpret_cast<unsigned char*>(p.lo_io) + (size_t)(m_first >> 4) * 16 * p.ldc + (size_t)((nn >> 3)) * 128 + r8 * 16, lo4);
+          // (a band's second row may lie past the live rows while its first does not: only the first row's 8-byte half is stored then --
+          //  with a device-side row count the row behind it is a real row of the plane, not padding, and is not this call's to write)
+          unsigned char* lo_dst = reinterpret_cast<unsigned char*>(p.lo_io) + (size_t)(m_first >> 4) * 16 * p.ldc + (size_t)((nn >> 3)) * 128 + r8 * 16;
+          if (m_first + 8 < Mrt) store16(lo_dst, lo4);
+          else if (m_first < Mrt) *reinterpret_cast<u32x2*>(lo_dst) = u32x2{lo4[0], lo4[1]};
         }
         __builtin_amdgcn_wave_barrier();
         continue;

@@ -29,8 +29,11 @@ int plipmi_gemm_nt_traced(int dtype, int epilogue, int variant, int M, int N, in
   return PLIPMI_OK;
 }
 
-int plipmi_gemm_nt_ln(int dtype, int mode, int variant, int M, int N, int K, const void* A, const void* W, const float* bias,
-                      const float* stats, int ns, float eps, void* C, void* xb_out, float* st_out, void* stream) {
+}  // extern "C"
+
+// plipmi_gemm_nt_ln / plipmi_gemm_nt_ln_rows: the latter with the live row count on the device
+static int gemm_nt_ln_entry(int dtype, int mode, int variant, int M, int N, int K, const void* A, const void* W, const float* bias,
+                            const float* stats, int ns, float eps, void* C, void* xb_out, float* st_out, const int* m_dev, void* stream) {
   if (!half_code(dtype)) return fail(PLIPMI_ERR_INVALID, "LayerNorm-folded epilogues are 16-bit-engine forms");
   if (mode < 0 || mode > 4 || M < 0 || N <= 0 || K <= 0 || !A || !W || !C || !bias) return fail(PLIPMI_ERR_INVALID, "bad argument");
   if (mode < 2 && (!stats || ns <= 0)) return fail(PLIPMI_ERR_INVALID, "mode 0/1 need the row statistics");
@@ -38,6 +41,7 @@ int plipmi_gemm_nt_ln(int dtype, int mode, int variant, int M, int N, int K, con
   if (mode >= 2 && (!xb_out || !st_out || N % kLnSlice)) return fail(PLIPMI_ERR_INVALID, "mode 2/3 need xb_out, st_out and N %% 64 == 0");
   if (mode >= 3 && variant == -3) return fail(PLIPMI_ERR_INVALID, "the small-M kernel has no split-plane epilogue");
   GemmParams p = make_params(A, W, C, bias, M, N, K, K, K, N);
+  p.m_dev = m_dev;
   p.ln_stats = stats; p.ln_ns = ns; p.ln_inv_d = ns > 0 ? 1.0f / (float)(ns * kLnSlice) : 0.f; p.ln_eps = eps;
   p.xb_out = xb_out; p.st_out = st_out;
   if (mode >= 3) { p.lo_io = C; p.C = nullptr; p.planes_other = mode == 4; }
@@ -49,12 +53,35 @@ int plipmi_gemm_nt_ln(int dtype, int mode, int variant, int M, int N, int K, con
   return PLIPMI_OK;
 }
 
+extern "C" {
+
+int plipmi_gemm_nt_ln(int dtype, int mode, int variant, int M, int N, int K, const void* A, const void* W, const float* bias,
+                      const float* stats, int ns, float eps, void* C, void* xb_out, float* st_out, void* stream) {
+  return gemm_nt_ln_entry(dtype, mode, variant, M, N, K, A, W, bias, stats, ns, eps, C, xb_out, st_out, nullptr, stream);
+}
+int plipmi_gemm_nt_ln_rows(int dtype, int mode, int variant, int M, int N, int K, const void* A, const void* W, const float* bias,
+                           const float* stats, int ns, float eps, void* C, void* xb_out, float* st_out, const int32_t* m_dev,
+                           void* stream) {
+  if (!m_dev) return fail(PLIPMI_ERR_INVALID, "null m_dev (plipmi_gemm_nt_ln is the form without a device-side row count)");
+  if (variant < -1) return fail(PLIPMI_ERR_INVALID, "variant %d does not read a device-side row count: -1 or a tile", variant);
+  return gemm_nt_ln_entry(dtype, mode, variant, M, N, K, A, W, bias, stats, ns, eps, C, xb_out, st_out, m_dev, stream);
+}
+
 int plipmi_attention(int dtype, int impl, const void* qkv, void* out, int B, int S, int H, int causal,
                      const int64_t* key_mask, void* stream) {
   if (!valid_dtype(dtype) || !qkv || !out || B < 0 || S <= 0 || H <= 0)
     return fail(PLIPMI_ERR_INVALID, "bad argument");
   hipError_t e = launch_attention(qkv, out, dtype, B, S, H, causal, key_mask, impl, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(PLIPMI_ERR_HIP, "attention launch (impl %d, S=%d) failed: %s", impl, S, hipGetErrorString(e));
+  return PLIPMI_OK;
+}
+
+int plipmi_attention_packed(int dtype, int impl, const void* qkv, void* out, int B, int S, int H, int causal, const int64_t* key_mask,
+                            const int32_t* cu, void* stream) {
+  if (!half_code(dtype) || !qkv || !out || !cu || B < 0 || S <= 0 || H <= 0) return fail(PLIPMI_ERR_INVALID, "bad argument (16-bit dtype, qkv, out, cu non-null)");
+  if (impl != 1 || S > 128) return fail(PLIPMI_ERR_INVALID, "packed rows are a form of the short-sequence MFMA kernel: impl 1, S <= 128 (got impl %d, S=%d)", impl, S);
+  hipError_t e = launch_attention(qkv, out, dtype, B, S, H, causal, key_mask, impl, reinterpret_cast<hipStream_t>(stream), cu);
+  if (e != hipSuccess) return fail(PLIPMI_ERR_HIP, "packed attention launch (S=%d) failed: %s", S, hipGetErrorString(e));
   return PLIPMI_OK;
 }
 
@@ -207,6 +234,61 @@ int plipmi_head_gemm(const float* A, const float* W, float* C, int M, int N, int
 int plipmi_recode_planes(void* hi, void* lo, size_t rows, int D, int from_dtype, int to_dtype, void* stream) {
   if (!hi || !lo || D <= 0 || D % 8) return fail(PLIPMI_ERR_INVALID, "null planes / width not a multiple of 8");
   HIP_TRY(launch_recode_planes(hi, lo, rows, D, from_dtype, to_dtype, reinterpret_cast<hipStream_t>(stream)));
+  return PLIPMI_OK;
+}
+
+// ---- the vision front end, kernel by kernel (towers.hip vision_embed) --------------------------------------------------------------
+int plipmi_unfold_patches(int dtype, int from_u8, const void* src, void* out, int B, int H, int W, int patch, int Kpad, void* stream) {
+  if (!valid_dtype(dtype) || (from_u8 != 0 && from_u8 != 1) || !src || !out || B < 0) return fail(PLIPMI_ERR_INVALID, "bad argument");
+  if (patch <= 0 || patch > 64 || H < patch || W < patch || H > 16384 || W > 16384)
+    return fail(PLIPMI_ERR_INVALID, "patch %d / image %d x %d: 1 <= patch <= 64, at least one patch, sides <= 16384", patch, H, W);
+  if (Kpad < 3 * patch * patch || Kpad % 4) return fail(PLIPMI_ERR_INVALID, "Kpad %d: >= 3 * patch^2 = %d and a multiple of 4", Kpad, 3 * patch * patch);
+  if (((uintptr_t)src | (uintptr_t)out) % 16) return fail(PLIPMI_ERR_INVALID, "src / out must be 16-byte aligned");
+  if ((size_t)B * (H / patch) * (W / patch) > 0x7fffffffull) return fail(PLIPMI_ERR_INVALID, "more than 2^31 - 1 patch rows");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (from_u8) HIP_TRY(launch_unfold_patches_u8(static_cast<const uint8_t*>(src), out, dtype, B, H, W, patch, Kpad, s));
+  else HIP_TRY(launch_unfold_patches(static_cast<const float*>(src), out, dtype, B, H, W, patch, Kpad, s));
+  return PLIPMI_OK;
+}
+int plipmi_cls_rows(const float* cls, const float* pos, float* x, int B, int tokens, int D, void* stream) {
+  if (!cls || !pos || !x || B < 0 || tokens < 1 || D <= 0 || D % 4) return fail(PLIPMI_ERR_INVALID, "bad argument (tokens >= 1, D %% 4 == 0)");
+  if (((uintptr_t)cls | (uintptr_t)pos | (uintptr_t)x) % 16) return fail(PLIPMI_ERR_INVALID, "cls / pos / x must be 16-byte aligned");
+  HIP_TRY(launch_cls_rows(cls, pos, x, B, tokens, D, reinterpret_cast<hipStream_t>(stream)));
+  return PLIPMI_OK;
+}
+int plipmi_gemm_patch(int dtype, int variant, int M, int N, int K, const void* A, int lda, const void* W, int ldw, const float* pos,
+                      int np, void* C, void* stream) {
+  if (!valid_dtype(dtype)) return fail(PLIPMI_ERR_INVALID, "bad dtype");
+  const int per16 = dtype == PLIPMI_F32 ? 4 : 8;
+  if (M < 0 || N <= 0 || N % 4 || K <= 0 || !A || !W || !C || !pos || lda < K || ldw < K || lda % per16 || ldw % per16)
+    return fail(PLIPMI_ERR_INVALID, "bad shape / null pointer / leading dimension (N %% 4 == 0; lda, ldw >= K and multiples of 16 bytes)");
+  if (np <= 0 || M % np) return fail(PLIPMI_ERR_INVALID, "np = %d patches per image must be positive and divide M = %d", np, M);
+  if (variant < -2) return fail(PLIPMI_ERR_INVALID, "variant %d: -1 (cost model), -2 (naive checker) or a tile", variant);
+  GemmParams p = make_params(A, W, C, pos, M, N, K, lda, ldw, N);
+  p.np = np;
+  const int rc = gemm_launch(dtype, EPI_PATCH, variant, p, reinterpret_cast<hipStream_t>(stream), nullptr);
+  if (rc != 0) return fail(PLIPMI_ERR_HIP, "patch gemm launch failed (variant %d, M=%d N=%d K=%d): %s", variant, M, N, K,
+                           hipGetErrorString((hipError_t)rc));
+  return PLIPMI_OK;
+}
+int plipmi_gemm_patch_gather(int dtype, const float* pixels, const uint8_t* tiles, const void* W, const float* pos, float* C, int B,
+                             int H, int W_px, int patch, int N, void* stream) {
+  // what gemm_gather_supports and gemm_launch_gather refuse, without the cost-model clause (this entry runs the ring tile at any batch)
+  if (!half_code(dtype)) return fail(PLIPMI_ERR_INVALID, "im2col on load is a 16-bit-engine form");
+  if ((pixels != nullptr) == (tiles != nullptr) || !W || !pos || !C || B < 0) return fail(PLIPMI_ERR_INVALID, "bad argument (exactly one of pixels / tiles; W, pos, C non-null)");
+  if (patch != 16 && patch != 32) return fail(PLIPMI_ERR_INVALID, "patch %d: the gather takes 16- and 32-pixel patches", patch);
+  if (H < patch || W_px < patch || W_px % 4) return fail(PLIPMI_ERR_INVALID, "image %d x %d: at least one patch, width %% 4 == 0", H, W_px);
+  if (N <= 0 || N % 256) return fail(PLIPMI_ERR_INVALID, "N = %d: whole 256-column tiles", N);
+  const int np = (H / patch) * (W_px / patch), K = 3 * patch * patch;
+  const size_t M = (size_t)B * np;
+  if ((size_t)B * 3 * H * W_px * 4 >= (1ull << 32) || (M + B + 1) * N * 4 >= (1ull << 32) || (size_t)N * K * 2 >= (1ull << 32))
+    return fail(PLIPMI_ERR_INVALID, "pixels, output rows and weights must each stay below 4 GiB (32-bit buffer offsets)");
+  // GemmParams as vision_embed fills them (kpad == K for these patch sides)
+  GemmParams p = make_params(nullptr, W, C, pos, (int)M, N, K, K, K, N);
+  p.np = np;
+  p.pix = pixels; p.tiles = tiles; p.img_h = H; p.img_w = W_px; p.patch_log2 = patch == 32 ? 5 : 4;
+  const int rc = gemm_launch_gather(dtype, p, reinterpret_cast<hipStream_t>(stream), nullptr);
+  if (rc != 0) return fail(PLIPMI_ERR_HIP, "patch GEMM (im2col on load) failed: %s", hipGetErrorString((hipError_t)rc));
   return PLIPMI_OK;
 }
 

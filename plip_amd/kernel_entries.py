@@ -410,3 +410,115 @@ def resize_ragged_tables(in_size: int, out_size: int, first: int = 0, count: Opt
         _lib.check(lib.plipmi_resize_ragged_tables(int(in_size), int(out_size), int(first), count, int(ksize), _ptr(bounds), _ptr(coef),
                                                    _stream(bounds)), "plipmi_resize_ragged_tables")
     return bounds, coef
+
+
+# ---- the vision front end and the packed-row mechanisms (include/plipmi_test.h, tests/test_gpu_front_end.py) ---------------------------
+# Every wrapper here writes into buffers the CALLER allocates (and may have pre-filled with a sentinel, with guard rows behind them):
+# what a kernel leaves alone is part of what the tests check.
+def patch_kpad(patch: int) -> int:
+    """the patch rows' padded width: 3 * patch^2 rounded up to 64 (csrc/handle_host.h init_model)"""
+    return (3 * patch * patch + 63) // 64 * 64
+
+
+def unfold_patches(src: torch.Tensor, out: torch.Tensor, patch: int, kpad: int) -> torch.Tensor:
+    """``plipmi_unfold_patches``: src fp32 [B, 3, H, W] or uint8 tiles [B, H, W, 3] -> rows 0 .. B * (H // patch) * (W // patch) - 1 of
+    ``out`` [>= that many rows, kpad] (fp32 / bf16 / f16)."""
+    lib = _lib.load()
+    assert src.is_cuda and out.is_cuda and src.is_contiguous() and out.is_contiguous() and src.dim() == 4 and out.dim() == 2
+    u8 = src.dtype == torch.uint8
+    assert u8 or src.dtype == torch.float32
+    B, H, W = (src.shape[0], src.shape[1], src.shape[2]) if u8 else (src.shape[0], src.shape[2], src.shape[3])
+    assert src.shape[3 if u8 else 1] == 3 and out.shape[1] == kpad and out.shape[0] >= B * (H // patch) * (W // patch)
+    with torch.cuda.device(src.device):
+        _lib.check(lib.plipmi_unfold_patches(_code(out.dtype), int(u8), _ptr(src), _ptr(out), B, H, W, int(patch), int(kpad), _stream(src)),
+                   "plipmi_unfold_patches")
+    return out
+
+
+def cls_rows(cls: torch.Tensor, pos: torch.Tensor, x: torch.Tensor, B: int, tokens: int) -> torch.Tensor:
+    """``plipmi_cls_rows``: row 0 of each of the B images of x fp32 [>= B * tokens, D] = cls [D] + pos[0] (pos fp32 [>= 1, D])."""
+    lib = _lib.load()
+    _f32(cls, pos, x)
+    D = cls.numel()
+    assert pos.shape[-1] == D and x.dim() == 2 and x.shape[1] == D and x.shape[0] >= B * tokens
+    with torch.cuda.device(x.device):
+        _lib.check(lib.plipmi_cls_rows(_ptr(cls), _ptr(pos), _ptr(x), int(B), int(tokens), D, _stream(x)), "plipmi_cls_rows")
+    return x
+
+
+def gemm_patch(a: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, out: torch.Tensor, K: Optional[int] = None, variant: int = -1) -> torch.Tensor:
+    """``plipmi_gemm_patch`` (the EPI_PATCH epilogue): a [B * np, lda], w [N, ldw] (K <= lda, ldw columns used; default all of a's),
+    pos fp32 [np + 1, N] -> token rows img * (np + 1) + 1 + p of ``out`` fp32 [>= B * (np + 1), N]."""
+    lib = _lib.load()
+    assert a.is_cuda and w.is_cuda and a.dtype == w.dtype and a.is_contiguous() and w.is_contiguous()
+    _f32(pos, out)
+    M, N, np_ = a.shape[0], w.shape[0], pos.shape[0] - 1
+    K = a.shape[1] if K is None else int(K)
+    assert np_ >= 1 and M % np_ == 0 and pos.shape[1] == N and out.shape[1] == N and out.shape[0] >= M // np_ * (np_ + 1)
+    with torch.cuda.device(a.device):
+        _lib.check(lib.plipmi_gemm_patch(_code(a.dtype), int(variant), M, N, K, _ptr(a), a.shape[1], _ptr(w), w.shape[1], _ptr(pos), np_,
+                                         _ptr(out), _stream(a)), "plipmi_gemm_patch")
+    return out
+
+
+def gemm_patch_gather(src: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, out: torch.Tensor, patch: int) -> torch.Tensor:
+    """``plipmi_gemm_patch_gather`` (im2col on load, the ring tile at any batch): src fp32 [B, 3, H, W] or uint8 [B, H, W, 3], w [N, 3 * patch^2]
+    (bf16 / f16; fp32 is passed on to be refused), pos fp32 [np + 1, N] -> the token rows of ``out`` fp32 [>= B * (np + 1), N]."""
+    lib = _lib.load()
+    assert src.is_cuda and w.is_cuda and src.is_contiguous() and w.is_contiguous() and src.dim() == 4
+    _f32(pos, out)
+    u8 = src.dtype == torch.uint8
+    assert u8 or src.dtype == torch.float32
+    B, H, W = (src.shape[0], src.shape[1], src.shape[2]) if u8 else (src.shape[0], src.shape[2], src.shape[3])
+    N = w.shape[0]
+    assert out.shape[1] == N and pos.shape[1] == N and out.shape[0] >= B * pos.shape[0]
+    with torch.cuda.device(src.device):
+        _lib.check(lib.plipmi_gemm_patch_gather(_code(w.dtype), None if u8 else _ptr(src), _ptr(src) if u8 else None, _ptr(w), _ptr(pos),
+                                                _ptr(out), B, H, W, int(patch), N, _stream(src)), "plipmi_gemm_patch_gather")
+    return out
+
+
+def gemm_nt_ln_rows(mode: int, a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, m_dev: torch.Tensor, out, st: Optional[torch.Tensor] = None,
+                    stats: Optional[torch.Tensor] = None, M: Optional[int] = None, eps: float = 1e-5, variant: int = -1) -> None:
+    """``plipmi_gemm_nt_ln_rows``: ``gemm_nt_ln`` on the first min(m_dev[0], M) rows of a grid sized for M rows (default a.shape[0]), into
+    the caller's buffers: mode 0 / 1 ``out`` = C [>= M, N] (16-bit), modes 3 / 4 ``out`` = (hi [>= M, N], lo uint8) and ``st``
+    fp32 [>= M, N // 64, 2].  m_dev int32 [1] on the device; None runs ``plipmi_gemm_nt_ln`` itself (the same call without it)."""
+    lib = _lib.load()
+    assert a.dtype in (torch.bfloat16, torch.float16) and w.dtype == a.dtype and a.is_contiguous() and w.is_contiguous() and mode in (0, 1, 3, 4)
+    assert m_dev is None or (m_dev.is_cuda and m_dev.dtype == torch.int32 and m_dev.numel() == 1)
+    M = a.shape[0] if M is None else int(M)
+    K, N = a.shape[1], w.shape[0]
+    assert a.shape[0] >= M
+    if mode in (0, 1):
+        assert out.dtype == a.dtype and out.is_contiguous() and out.shape[1] == N and out.shape[0] >= M and stats.is_contiguous() and stats.shape[0] >= M
+        args = (_ptr(stats), stats.shape[1], float(eps), _ptr(out), None, None)
+    else:
+        hi, lo = out
+        assert hi.dtype == a.dtype and hi.is_contiguous() and hi.shape[1] == N and hi.shape[0] >= M and lo.dtype == torch.uint8 and lo.is_contiguous()
+        assert lo.numel() >= lo_plane_bytes(M, N) and st.is_contiguous() and st.shape[0] >= M and st.shape[1:] == (N // 64, 2)
+        args = (None, 0, float(eps), _ptr(lo), _ptr(hi), _ptr(st))
+    with torch.cuda.device(a.device):
+        if m_dev is None:
+            _lib.check(lib.plipmi_gemm_nt_ln(_code(a.dtype), mode, int(variant), M, N, K, _ptr(a), _ptr(w), _ptr(bias), *args, _stream(a)),
+                       "plipmi_gemm_nt_ln")
+        else:
+            _lib.check(lib.plipmi_gemm_nt_ln_rows(_code(a.dtype), mode, int(variant), M, N, K, _ptr(a), _ptr(w), _ptr(bias), *args, _ptr(m_dev),
+                                                  _stream(a)), "plipmi_gemm_nt_ln_rows")
+
+
+def attention_packed(qkv: torch.Tensor, out: torch.Tensor, cu: torch.Tensor, S: int, H: int, causal: bool = False,
+                     key_mask: Optional[torch.Tensor] = None, impl: int = 1) -> torch.Tensor:
+    """``plipmi_attention_packed``: qkv [rows, 3 * H * 64] packed rows, cu int32 [B + 1] (caption b = rows cu[b] .. cu[b + 1] - 1, each
+    1 .. S long), key_mask int64 [B, S] or None -> rows 0 .. cu[B] - 1 of ``out`` [>= cu[B], H * 64]."""
+    lib = _lib.load()
+    assert qkv.is_cuda and qkv.is_contiguous() and out.is_contiguous() and qkv.shape[1] == 3 * H * 64 and out.shape[1] == H * 64 and out.dtype == qkv.dtype
+    assert cu.is_cuda and cu.dtype == torch.int32 and cu.dim() == 1
+    B = cu.numel() - 1
+    c = cu.cpu()
+    ln = c[1:] - c[:-1]
+    assert int(c[0]) == 0 and (B == 0 or (int(ln.min()) >= 1 and int(ln.max()) <= max(S, 1))) and int(c[-1]) <= min(qkv.shape[0], out.shape[0])
+    assert key_mask is None or (key_mask.is_cuda and key_mask.dtype == torch.int64 and key_mask.is_contiguous() and key_mask.shape == (B, S))
+    with torch.cuda.device(qkv.device):
+        _lib.check(lib.plipmi_attention_packed(_code(qkv.dtype), int(impl), _ptr(qkv), _ptr(out), B, int(S), H, int(causal), _ptr(key_mask),
+                                               _ptr(cu), _stream(qkv)), "plipmi_attention_packed")
+    return out

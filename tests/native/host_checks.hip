@@ -351,6 +351,45 @@ static void check_early_returns() {
   REJECTS(plipmi_head_gemm(nullptr, f, f, 1, 32, 32, 1.f, nullptr), "N % 32 == 0");
   REJECTS(plipmi_recode_planes(nullptr, f, 1, 8, 1, 2, nullptr), "null planes");
   REJECTS(plipmi_recode_planes(f, f, 1, 12, 1, 2, nullptr), "null planes");
+  // the vision front end and the packed-row mechanisms
+  REJECTS(plipmi_unfold_patches(3, 0, x16, x16, 1, 16, 16, 16, 768, nullptr), "bad argument");
+  REJECTS(plipmi_unfold_patches(0, 2, x16, x16, 1, 16, 16, 16, 768, nullptr), "bad argument");
+  REJECTS(plipmi_unfold_patches(0, 0, nullptr, x16, 1, 16, 16, 16, 768, nullptr), "bad argument");
+  REJECTS(plipmi_unfold_patches(0, 0, x16, x16, 1, 16, 15, 16, 768, nullptr), "at least one patch");
+  REJECTS(plipmi_unfold_patches(0, 0, x16, x16, 1, 16, 16, 0, 768, nullptr), "1 <= patch <= 64");
+  REJECTS(plipmi_unfold_patches(1, 0, x16, x16, 1, 16, 16, 16, 764, nullptr), "Kpad 764");
+  REJECTS(plipmi_unfold_patches(1, 1, x16, x16, 1, 15, 15, 15, 678, nullptr), "Kpad 678");
+  REJECTS(plipmi_unfold_patches(0, 0, x16 + 1, x16, 1, 16, 16, 16, 768, nullptr), "16-byte aligned");
+  REJECTS(plipmi_cls_rows(nullptr, x16, x16, 1, 2, 4, nullptr), "bad argument");
+  REJECTS(plipmi_cls_rows(x16, x16, x16, 1, 0, 4, nullptr), "tokens >= 1");
+  REJECTS(plipmi_cls_rows(x16, x16, x16, 1, 2, 6, nullptr), "D % 4 == 0");
+  REJECTS(plipmi_cls_rows(x16, x16 + 1, x16, 1, 2, 4, nullptr), "16-byte aligned");
+  REJECTS(plipmi_gemm_patch(3, -1, 4, 4, 4, f, 4, f, 4, f, 2, f, nullptr), "bad dtype");
+  REJECTS(plipmi_gemm_patch(0, -1, 4, 6, 4, f, 4, f, 4, f, 2, f, nullptr), "leading dimension");
+  REJECTS(plipmi_gemm_patch(0, -1, 4, 4, 4, f, 3, f, 4, f, 2, f, nullptr), "leading dimension");
+  REJECTS(plipmi_gemm_patch(1, -1, 4, 4, 8, f, 8, f, 12, f, 2, f, nullptr), "leading dimension");
+  REJECTS(plipmi_gemm_patch(0, -1, 4, 4, 4, f, 4, f, 4, nullptr, 2, f, nullptr), "null pointer");
+  REJECTS(plipmi_gemm_patch(0, -1, 4, 4, 4, f, 4, f, 4, f, 0, f, nullptr), "np = 0");
+  REJECTS(plipmi_gemm_patch(0, -1, 4, 4, 4, f, 4, f, 4, f, 3, f, nullptr), "np = 3");
+  REJECTS(plipmi_gemm_patch(0, -3, 4, 4, 4, f, 4, f, 4, f, 2, f, nullptr), "variant -3");
+  REJECTS(plipmi_gemm_patch_gather(0, f, nullptr, f, f, f, 1, 16, 16, 16, 256, nullptr), "16-bit-engine form");
+  REJECTS(plipmi_gemm_patch_gather(1, nullptr, nullptr, f, f, f, 1, 16, 16, 16, 256, nullptr), "exactly one of pixels / tiles");
+  REJECTS(plipmi_gemm_patch_gather(1, f, u8, f, f, f, 1, 16, 16, 16, 256, nullptr), "exactly one of pixels / tiles");
+  REJECTS(plipmi_gemm_patch_gather(1, f, nullptr, nullptr, f, f, 1, 16, 16, 16, 256, nullptr), "exactly one of pixels / tiles");
+  REJECTS(plipmi_gemm_patch_gather(2, f, nullptr, f, f, f, 1, 28, 28, 14, 256, nullptr), "patch 14");
+  REJECTS(plipmi_gemm_patch_gather(1, f, nullptr, f, f, f, 1, 48, 50, 16, 256, nullptr), "width % 4 == 0");
+  REJECTS(plipmi_gemm_patch_gather(1, nullptr, u8, f, f, f, 1, 15, 16, 16, 256, nullptr), "at least one patch");
+  REJECTS(plipmi_gemm_patch_gather(1, f, nullptr, f, f, f, 1, 16, 16, 16, 128, nullptr), "whole 256-column tiles");
+  REJECTS(plipmi_gemm_patch_gather(1, f, nullptr, f, f, f, 400, 1024, 1024, 16, 256, nullptr), "below 4 GiB");
+  REJECTS(plipmi_gemm_nt_ln_rows(1, 0, -1, 4, 128, 128, f, f, f, f, 2, 1e-5f, f, f, f, nullptr, nullptr), "null m_dev");
+  REJECTS(plipmi_gemm_nt_ln_rows(1, 0, -2, 4, 128, 128, f, f, f, f, 2, 1e-5f, f, f, f, i32, nullptr), "variant -2 does not read");
+  REJECTS(plipmi_gemm_nt_ln_rows(2, 0, -3, 4, 128, 128, f, f, f, f, 2, 1e-5f, f, f, f, i32, nullptr), "variant -3 does not read");
+  REJECTS(plipmi_gemm_nt_ln_rows(0, 0, -1, 4, 128, 128, f, f, f, f, 2, 1e-5f, f, f, f, i32, nullptr), "16-bit-engine forms");
+  REJECTS(plipmi_gemm_nt_ln_rows(1, 1, 0, 4, 128, 128, f, f, f, f, 3, 1e-5f, f, f, f, i32, nullptr), "must be even");
+  REJECTS(plipmi_attention_packed(0, 1, f, f, 1, 4, 1, 0, nullptr, i32, nullptr), "bad argument");
+  REJECTS(plipmi_attention_packed(1, 1, f, f, 1, 4, 1, 0, nullptr, nullptr, nullptr), "bad argument");
+  REJECTS(plipmi_attention_packed(1, 0, f, f, 1, 4, 1, 0, nullptr, i32, nullptr), "impl 1, S <= 128 (got impl 0");
+  REJECTS(plipmi_attention_packed(2, 1, f, f, 1, 129, 1, 1, nullptr, i32, nullptr), "S=129");
   CHECK(plipmi_gemm_variant_built(3, 0) == 0 && plipmi_gemm_variant_built(-1, 0) == 0);
   CHECK(plipmi_gemm_variant_name(-1) == nullptr && plipmi_gemm_variant_name(1 << 20) == nullptr);
   CHECK(plipmi_gemm_variant_name(0) != nullptr && strlen(plipmi_gemm_variant_name(0)) > 0);

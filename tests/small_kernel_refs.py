@@ -1,5 +1,5 @@
-"""Shared by tests/test_small_kernel_refs_host.py and tests/test_gpu_small_kernels.py (and tests/test_gpu_gemm.py for ``slice_stats``):
-plain float64 torch restatements of the kernels around the GEMMs (plip_amd/csrc/kernels.hip, attention_probs.hip), written from
+"""Shared by tests/test_small_kernel_refs_host.py, tests/test_gpu_small_kernels.py and tests/test_gpu_front_end.py (and tests/test_gpu_gemm.py
+for ``slice_stats``): plain float64 torch restatements of the kernels around the GEMMs (plip_amd/csrc/kernels.hip, attention_probs.hip), written from
 the operations' definitions and not from the kernels.  Each is checked on the CPU against an independent formulation
 (torch.nn.functional, numpy, oracle/clip_oracle.py) by the host test; the GPU test compares the kernels with them.
 
@@ -102,6 +102,47 @@ def pooled_head(x, ids, eos_id, ln_w, ln_b, eps, W=None, normalize=False, dtype=
         return y
     y = y @ W.to(dtype).T
     return y / torch.sqrt((y * y).sum(-1, keepdim=True)) if normalize else y
+
+
+# ---- the vision front end: patch unfold, patch embedding, uint8 normalisation -----------------------------------------------------------
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def unfold_ref(px, P, kpad=None):
+    """Conv2d(kernel = stride = P) as a re-index of px [B, 3, H, W]: row (b, gi, gj) of the floored (H // P) x (W // P) grid, column
+    (c, u, v) = px[b, c, gi * P + u, gj * P + v] -- the order of conv.weight.reshape(out, -1) --, zeros in columns 3 P^2 .. kpad.
+    Same dtype as px: nothing is computed."""
+    B, C, H, W = px.shape
+    gh, gw, K = H // P, W // P, C * P * P
+    out = torch.zeros(B * gh * gw, K if kpad is None else kpad, dtype=px.dtype)
+    for gi in range(gh):
+        for gj in range(gw):
+            cell = px[:, :, gi * P:(gi + 1) * P, gj * P:(gj + 1) * P].reshape(B, K)
+            out[gi * gw + gj::gh * gw, :K] = cell                        # rows b * gh * gw + gi * gw + gj, b = 0 .. B - 1
+    return out
+
+
+def patch_embed_ref(px, w, P, pos, cls=None):
+    """CLIPVisionEmbeddings in float64: conv2d(px [B, 3, H, W], w [N, 3 P^2] viewed [N, 3, P, P], stride P), flattened to token rows
+    [B, np + 1, N] with pos [np + 1, N] added; row 0 of each image is cls + pos[0] (NaN without cls: rows the patch GEMM does not own).
+    px and w are taken as given -- the caller passes the operands already rounded to the kernel's type."""
+    N = w.shape[0]
+    y = torch.nn.functional.conv2d(px.to(F64), w.to(F64).reshape(N, 3, P, P), stride=P)      # [B, N, gh, gw]
+    y = y.flatten(2).transpose(1, 2) + pos.to(F64)[None, 1:]
+    first = torch.full((N,), float("nan"), dtype=F64) if cls is None else cls.to(F64) + pos.to(F64)[0]
+    return torch.cat((first[None, None].expand(y.shape[0], 1, N), y), dim=1)
+
+
+def u8_norm_ref(tiles):
+    """uint8 HWC tiles [B, H, W, 3] -> fp32 NCHW pixels, the reference transform's three fp32 roundings: (b / 255 - mean_c) * (1 / std_c)
+    with 1 / std_c itself rounded to fp32 -- the mirror tests/test_host.py proves the one-fma form against."""
+    b = tiles.numpy().astype(np.float32)
+    mean = np.array(CLIP_MEAN, dtype=np.float32)
+    istd = (np.float32(1.0) / np.array(CLIP_STD, dtype=np.float32)).astype(np.float32)
+    x = (b / np.float32(255.0)).astype(np.float32)
+    x = ((x - mean).astype(np.float32) * istd).astype(np.float32)
+    return torch.from_numpy(np.ascontiguousarray(x.transpose(0, 3, 1, 2)))
 
 
 # ---- top-k, arg-max ------------------------------------------------------------------------------------------------------------------

@@ -175,3 +175,73 @@ def test_tolerance_helpers():
     assert abs(err - 2.0 ** -20) < 1e-12 and bound == 4 * err
     assert R.fp32_bound(ref.float(), ref)[0] == R.ulp32(3.0)                # floor: one fp32 ulp of the largest magnitude
     assert R.fp32_bound(cpu, ref, cap=1e-7)[0] == 1e-7
+
+
+# ---- the vision front end (tests/test_gpu_front_end.py) ---------------------------------------------------------------------------------
+FRONT_END_CASES = [(32, 64, 96), (16, 52, 72), (16, 48, 50), (14, 30, 44), (15, 31, 47)]
+
+
+@pytest.mark.parametrize("P,H,W", FRONT_END_CASES)
+def test_unfold_ref_is_torch_unfold_with_zero_padding(P, H, W):
+    B, K = 3, 3 * P * P
+    kpad = (K + 63) // 64 * 64
+    px = torch.randn(B, 3, H, W, generator=_gen(P * H)).double()
+    got = R.unfold_ref(px, P, kpad)
+    gh, gw = H // P, W // P
+    want = F.unfold(px[:, :, :gh * P, :gw * P], kernel_size=P, stride=P).transpose(1, 2).reshape(B * gh * gw, K)
+    assert got.shape == (B * gh * gw, kpad) and torch.equal(got[:, :K], want)
+    assert (got[:, K:] == 0).all()
+    # element by element on a few rows, from the definition
+    for row, k in ((0, 0), (B * gh * gw - 1, K - 1), (gw + 1 if gh > 1 and gw > 1 else 0, P * P + P + 1)):
+        b, cell = divmod(row, gh * gw)
+        gi, gj = divmod(cell, gw)
+        c, rem = divmod(k, P * P)
+        u, v = divmod(rem, P)
+        assert got[row, k] == px[b, c, gi * P + u, gj * P + v]
+    # the remainder pixels the grid floors away never appear: poisoning them changes nothing
+    px2 = px.clone()
+    px2[:, :, gh * P:, :] = float("nan")
+    px2[:, :, :, gw * P:] = float("nan")
+    assert torch.equal(R.unfold_ref(px2, P, kpad), got)
+
+
+@pytest.mark.parametrize("P,H,W", FRONT_END_CASES)
+def test_patch_embed_ref_is_the_unfolded_rows_times_the_weights(P, H, W):
+    """unfold_ref @ W^T + pos == the conv2d form, CLS rows cls + pos[0]"""
+    B, N, K = 3, 24, 3 * P * P
+    g0 = _gen(W)
+    px = torch.randn(B, 3, H, W, generator=g0).double()
+    w = torch.randn(N, K, generator=g0).double() / K ** 0.5
+    np_ = (H // P) * (W // P)
+    pos, cls = torch.randn(np_ + 1, N, generator=g0).double(), torch.randn(N, generator=g0).double()
+    ref = R.patch_embed_ref(px, w, P, pos, cls)
+    assert ref.shape == (B, np_ + 1, N)
+    rows = R.unfold_ref(px, P, (K + 63) // 64 * 64)[:, :K] @ w.T
+    want = rows.reshape(B, np_, N) + pos[None, 1:]
+    assert (ref[:, 1:] - want).abs().max().item() < 1e-12
+    assert torch.equal(ref[:, 0], (cls + pos[0])[None].expand(B, N))
+    assert torch.isnan(R.patch_embed_ref(px, w, P, pos)[:, 0]).all()
+    # against HF's module arithmetic: conv -> flatten(2).transpose(1, 2), cat with the class row, + position embedding
+    conv = F.conv2d(px, w.reshape(N, 3, P, P), stride=P).flatten(2).transpose(1, 2)
+    hf = torch.cat((cls.expand(B, 1, N), conv), dim=1) + pos[None]
+    assert (ref - hf).abs().max().item() < 1e-12
+
+
+def test_u8_norm_ref_is_three_fp32_roundings_per_byte():
+    """every byte value and channel, against scalar numpy float32 arithmetic, and within fp32 round-off of the float64 transform"""
+    tiles = torch.arange(256, dtype=torch.uint8).reshape(1, 16, 16, 1).expand(1, 16, 16, 3).contiguous()
+    got = R.u8_norm_ref(tiles)
+    assert got.dtype == torch.float32 and got.shape == (1, 3, 16, 16)
+    for c in range(3):
+        mean, istd = np.float32(R.CLIP_MEAN[c]), np.float32(1.0) / np.float32(R.CLIP_STD[c])
+        for b in range(256):
+            x = np.float32(np.float32(b) / np.float32(255.0))
+            x = np.float32(np.float32(x - mean) * istd)
+            assert got[0, c, b // 16, b % 16].item() == float(x), (c, b)
+        exact = (np.arange(256, dtype=np.float64) / 255.0 - R.CLIP_MEAN[c]) / R.CLIP_STD[c]
+        assert np.abs(got[0, c].reshape(-1).numpy().astype(np.float64) - exact).max() < 4 * 2.0 ** -24 * 3
+    # the layout: HWC bytes -> NCHW planes
+    t2 = torch.randint(0, 256, (2, 5, 7, 3), generator=_gen(5), dtype=torch.uint8)
+    g2 = R.u8_norm_ref(t2)
+    assert g2.shape == (2, 3, 5, 7)
+    assert g2[1, 2, 4, 6].item() == got[0, 2].reshape(-1)[int(t2[1, 4, 6, 2])].item()
