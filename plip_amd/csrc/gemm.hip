@@ -1,4 +1,4 @@
-// gemm.hip -- variant registry and dispatch for the NT GEMM (kernels live in gemm.h).
+// gemm.hip -- variant registry and dispatch for the NT GEMM (the kernels live in gemm_kernel.h).
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -143,7 +143,7 @@ int gemm_launch(int dtype, int epi, int variant, const GemmParams& p, hipStream_
   return fn(pr, stream);
 }
 
-// The patch GEMM with im2col on load (gemm.h ADDR 2): C rows = patches, A gathered from the fp32 NCHW pixels.  Applies to 16-bit
+// The patch GEMM with im2col on load (gemm_kernel.h ADDR 2): C rows = patches, A gathered from the fp32 NCHW pixels.  Applies to 16-bit
 // engines, patch sides 16 / 32 (whole 64-column K tiles of 4 / 2 patch rows), widths of whole 256-column tiles, and batches the cost
 // model gives the ring tile anyway; everything else keeps the unfold pass + the plain patch GEMM.
 // img_h x img_w images (plipmi_clone_resolution): the grid floors to (img_h / patch) x (img_w / patch); a row of img_w pixels must be a

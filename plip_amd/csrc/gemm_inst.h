@@ -3,7 +3,7 @@
 #pragma once
 #include <mutex>
 
-#include "gemm.h"
+#include "gemm_kernel.h"
 
 namespace plipmi {
 
@@ -11,9 +11,8 @@ typedef int (*GemmLaunchFn)(const GemmParams&, hipStream_t);
 
 template <typename T, int BM, int BN, int WM, int WN, int EPI, int SCHED = 0, int ADDR = 0, int NSTAGE = 2>
 int launch_tiled(const GemmParams& p, hipStream_t stream) {
-  constexpr int NT = WM * WN * 64;
-  // + rstd per tile row for the LayerNorm-folded epilogues
-  constexpr int LDS = NSTAGE * (BM + BN) * 128 + (epi_is_ln(EPI) ? BM * 4 : 0);
+  using TT = GemmTile<T, BM, BN, WM, WN, EPI, SCHED, ADDR, NSTAGE>;
+  constexpr int NT = TT::NT, LDS = TT::LDS_BYTES;
   auto kern = gemm_nt_kernel<T, BM, BN, WM, WN, EPI, SCHED, ADDR, NSTAGE>;
   // once per instantiation and process, also when two handles are created from two threads (a handle itself is not thread-safe)
   static std::once_flag attr_once;
@@ -29,7 +28,7 @@ int launch_tiled(const GemmParams& p, hipStream_t stream) {
 
 int gemm_num_cus();  // gemm.hip
 
-// The patch GEMM with im2col on load (gemm.h ADDR 2): the ring tile's EPI_PATCH kernel whose A operand is gathered from the fp32
+// The patch GEMM with im2col on load (gemm_kernel.h ADDR 2): the ring tile's EPI_PATCH kernel whose A operand is gathered from the fp32
 // pixels (GemmParams.pix); 16-bit types only.
 GemmLaunchFn gemm_get_gather_bf16();
 GemmLaunchFn gemm_get_gather_f16();

@@ -20,6 +20,7 @@
 // 400 rows), this kernel splits it 8 ways.  A row's result never depends on the other rows of ITS call, so embeddings are
 // bit-identical across batch sizes within each of the two regimes; between them they differ by fp32 summation order.
 #include "gemm.h"
+#include "gemm_lds.h"
 
 namespace plipmi {
 

@@ -22,6 +22,7 @@
 #include <mutex>
 
 #include "gemm.h"
+#include "gemm_lds.h"
 #include "kernels.h"
 
 namespace plipmi {

@@ -395,14 +395,14 @@ def test_split_plane_host_mirror_follows_the_format():
 
 
 def test_u8_normalisation_by_one_fma_is_exact_after_rounding():
-    """csrc/gemm.h ADDR 3 (im2col on load from uint8 tiles) normalises a byte of channel c as fl(b * A_c + B_c); the unfold kernel --
+    """csrc/gemm_fill.h ADDR 3 (im2col on load from uint8 tiles) normalises a byte of channel c as fl(b * A_c + B_c); the unfold kernel --
     and the reference's transform, reproducibility/embedders/transform.py:45-52 -- compute (b / 255 - mean_c) * (1 / std_c) in three fp32
     roundings.  The two agree after rounding to the operand type for EVERY byte value and channel, bf16 and f16: checked here on all
     2 x 3 x 256 cases with the kernel's constants (bit patterns) -- so the fused patch GEMM's A operand is the unfold pass's, bit for bit."""
     import numpy as np
-    src = open(os.path.join(ROOT, "plip_amd", "csrc", "gemm.h")).read()
+    src = open(os.path.join(ROOT, "plip_amd", "csrc", "gemm_fill.h")).read()
     m = re.search(r"const unsigned A\[3\] = \{(0x[0-9a-f]+)u, (0x[0-9a-f]+)u, (0x[0-9a-f]+)u\}, Bc\[3\] = \{(0x[0-9a-f]+)u, (0x[0-9a-f]+)u, (0x[0-9a-f]+)u\}", src)
-    assert m, "u8_norm's constants not found in gemm.h"
+    assert m, "u8_norm's constants not found in gemm_fill.h"
     bits = np.array([int(x, 16) for x in m.groups()], dtype=np.uint32)
     A, Bc = bits[:3].view(np.float32), bits[3:].view(np.float32)
     mean = np.array([0.48145466, 0.4578275, 0.40821073], dtype=np.float32)
