@@ -25,13 +25,20 @@ constexpr int kWave = 64;  // CDNA wavefront
 __device__ __forceinline__ float to_f32(float x) { return x; }
 __device__ __forceinline__ float to_f32(bf16_t x) { return (float)x; }
 __device__ __forceinline__ float to_f32(f16_t x) { return (float)x; }
-// fp32 -> half: values beyond the type's range SATURATE (+-65504) instead of becoming inf, so one outlier activation costs
-// accuracy on its own row, not NaNs through every softmax it reaches
-__device__ __forceinline__ float sat_f16(float x) { return __builtin_amdgcn_fmed3f(x, -65504.0f, 65504.0f); }
+// fp32 -> half: values beyond the type's range and +-inf SATURATE (+-65504) instead of becoming inf, so one outlier activation costs
+// accuracy on its own row, not NaNs through every softmax it reaches.  NaN PROPAGATES, as in the fp32 and bf16 engines.
+// Convert first (RNE; beyond 65520 -> inf), then clamp the half with the NaN-propagating IEEE 754-2019 minimum / maximum (gfx950:
+// v_pk_maximum3_f16 / v_pk_minimum3_f16, two values per instruction where neighbours are stored together) -- the same result as
+// clamping the fp32 value for every finite and infinite input.  NOT v_med3_f32(x, -65504, 65504): with a NaN operand it returns
+// min3 of the three, i.e. -65504, and a corrupt input comes out as a plausible finite embedding (tests/test_gpu_value_range.py).
+__device__ __forceinline__ f16_t sat_f16(float x) {
+  const f16_t h = (f16_t)x;
+  return __builtin_elementwise_minimum(__builtin_elementwise_maximum(h, (f16_t)-65504.0f), (f16_t)65504.0f);
+}
 template <typename T> __device__ __forceinline__ T from_f32(float x);
 template <> __device__ __forceinline__ float from_f32<float>(float x) { return x; }
 template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float x) { return (bf16_t)x; }  // RNE (v_cvt_pk_bf16_f32)
-template <> __device__ __forceinline__ f16_t from_f32<f16_t>(float x) { return (f16_t)sat_f16(x); }   // RNE (v_cvt_f16_f32)
+template <> __device__ __forceinline__ f16_t from_f32<f16_t>(float x) { return sat_f16(x); }   // RNE (v_cvt_f16_f32), saturating
 
 // the two 16-bit operand types: vector forms and the MFMA that multiplies them
 template <typename T> struct half_traits;
@@ -154,7 +161,7 @@ __device__ __forceinline__ unsigned f16_plane_exp(float hf) {   // biased fp32 e
   return eb < 113u ? 113u : eb;
 }
 template <> __device__ __forceinline__ void split_f32<f16_t>(float x, unsigned& hi16, unsigned& lo8) {
-  const f16_t h = (f16_t)sat_f16(x);
+  const f16_t h = sat_f16(x);
   const float hf = (float)h;
   const float scale = __builtin_bit_cast(float, (272u - f16_plane_exp(hf)) << 23);   // 2^(18 - E)
   const float r = __builtin_amdgcn_fmed3f(__builtin_rintf((x - hf) * scale), -127.0f, 127.0f);

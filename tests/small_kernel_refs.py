@@ -164,6 +164,47 @@ def first_argmax(x):
     return np.array([min(j for j in range(x.shape[1]) if row[j] == row.max()) for row in x], dtype=np.int64)
 
 
+# ---- the engines' 16-bit roundings (tests/test_gpu_value_range.py) ------------------------------------------------------------------
+def round_to(x64, dtype):
+    """float64 -> what a kernel's store of that value holds, ONE rounding from float64:
+    bf16: round to nearest even, overflow to inf, NaN stays NaN (torch's ``.to(bfloat16)`` of an fp32 value);
+    f16:  clamp to +-65504 (so +-inf too), then round to nearest even with gradual underflow, NaN stays NaN -- the engine's saturating
+          store (csrc/common.h from_f32<f16_t>).
+    Neither goes through fp32 with a second nearest rounding: f16 is numpy's float64 -> float16 conversion (correctly rounded), bf16
+    rounds float64 -> fp32 TO ODD first (truncate, set the last bit when inexact), after which the nearest-even step to 8 bits
+    rounds the original value."""
+    x = np.asarray(x64.detach().cpu().to(F64).numpy())
+    if dtype == torch.float32:
+        return torch.from_numpy(x.astype(np.float32))
+    if dtype == torch.float16:
+        with np.errstate(invalid="ignore"):
+            return torch.from_numpy(np.clip(x, -65504.0, 65504.0).astype(np.float16))        # np.clip keeps NaN
+    assert dtype == torch.bfloat16
+    nan = np.isnan(x)
+    xs = np.where(nan, 0.0, x)
+    with np.errstate(over="ignore"):
+        f = xs.astype(np.float32)                                                             # nearest; may be one step past xs
+    away = np.abs(f.astype(np.float64)) > np.abs(xs)
+    t = np.where(away, np.nextafter(f, np.float32(0)), f).astype(np.float32)                  # truncated towards zero (inf -> max)
+    inexact = t.astype(np.float64) != xs
+    bits = t.view(np.uint32) | inexact.astype(np.uint32)                                      # round to odd
+    out = torch.from_numpy(bits.view(np.float32).copy()).to(torch.bfloat16)                   # nearest even, overflow -> inf
+    out[torch.from_numpy(nan)] = float("nan")
+    return out
+
+
+def ord16(t):
+    """the bit patterns of a 16-bit float tensor as int32 ordinals that grow with the value (-0 and +0 both 0): the difference of two
+    is their distance in units in the last place"""
+    b = t.contiguous().view(torch.int16).to(torch.int32)
+    return torch.where(b < 0, -(b & 0x7FFF), b)
+
+
+def quick_gelu(x):
+    """x * sigmoid(1.702 x) (transformers/activations.py QuickGELUActivation)"""
+    return x * torch.sigmoid(1.702 * x)
+
+
 # ---- tolerances ----------------------------------------------------------------------------------------------------------------------
 def ulp32(v):
     """one fp32 unit in the last place at magnitude v (a float)"""

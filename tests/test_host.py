@@ -446,3 +446,25 @@ def test_named_test_hooks_reject_values_outside_their_range():
     out, ratio = C.c_void_p(1), C.c_float(0)
     assert lib.plipmi_clone(None, C.byref(out)) != 0 and "null" in _lib.last_error()          # no source handle: an error, no crash
     assert lib.plipmi_streams_overlap(None, None, None, C.byref(ratio)) != 0
+
+
+def test_isa_diff_compares_kernels_without_their_addresses():
+    """tools/isa_diff.py functions(): a kernel that only moved inside its code object (another kernel of the unit grew) compares
+    equal -- the address column is dropped, the encodings and the <symbol+offset> branch targets stay --, one changed instruction
+    or encoding does not"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("isa_diff", os.path.join(ROOT, "tools", "isa_diff.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+
+    def listing(base, second_op="v_add_f32_e32 v1, v0, v0", enc="02020100"):
+        return (f"{base:016x} <_Z1kv>:\n"
+                f"\ts_load_dwordx2 s[0:1], s[4:5], 0x0    // {base:012X}: C0060002 00000000\n"
+                f"\t{second_op}    // {base + 8:012X}: {enc}\n"
+                f"\ts_cbranch_scc1 65533    // {base + 12:012X}: BF85FFFD <_Z1kv+0x4>\n"
+                f"\n{base + 0x100:016x} <_Z2k2v>:\n"
+                f"\ts_endpgm    // {base + 0x100:012X}: BF810000\n")
+    a, moved = mod.functions(listing(0x1900)), mod.functions(listing(0x2A00))
+    assert set(a) == {"_Z1kv", "_Z2k2v"} and a == moved and "C0060002" in a["_Z1kv"] and "<_Z1kv+0x4>" in a["_Z1kv"]
+    assert mod.functions(listing(0x1900, "v_sub_f32_e32 v1, v0, v0", "04020100"))["_Z1kv"] != a["_Z1kv"]
+    assert mod.functions(listing(0x1900, enc="02020101"))["_Z1kv"] != a["_Z1kv"]

@@ -245,3 +245,103 @@ def test_u8_norm_ref_is_three_fp32_roundings_per_byte():
     g2 = R.u8_norm_ref(t2)
     assert g2.shape == (2, 3, 5, 7)
     assert g2[1, 2, 4, 6].item() == got[0, 2].reshape(-1)[int(t2[1, 4, 6, 2])].item()
+
+
+# ---- round_to: the 16-bit roundings the value-range GPU test compares the kernels' stores with ---------------------------------------
+def _rne_rational(x, p, emin):
+    """x (a finite float) rounded to nearest even on the grid of a binary format with p significand bits and smallest normal
+    exponent emin, in exact rational arithmetic; no overflow handling (the caller's values stay in range)"""
+    from fractions import Fraction
+    if x == 0:
+        return 0.0
+    fx = Fraction(abs(x))
+    e = emin
+    while fx >= Fraction(2) ** (e + 1):
+        e += 1
+    unit = Fraction(2) ** (e - (p - 1))                     # spacing of the binade (of the subnormals below 2^emin)
+    q, r = divmod(fx, unit)
+    if r * 2 > unit or (r * 2 == unit and q % 2 == 1):
+        q += 1
+    return float(q * unit) * (1 if x > 0 else -1)
+
+
+_FMT = {torch.bfloat16: (8, -126), torch.float16: (11, -14)}
+
+
+@pytest.mark.parametrize("dtype", list(_FMT), ids=["bf16", "f16"])
+def test_round_to_is_one_nearest_even_rounding_from_float64(dtype):
+    """against exact rational arithmetic: random values over the type's whole range, ties, near-ties that a detour through a
+    nearest fp32 would round the wrong way, subnormals"""
+    p, emin = _FMT[dtype]
+    g0 = _gen(11)
+    lo_e, hi_e = (emin - p - 2, 15) if dtype == torch.float16 else (emin - p - 2, 126)
+    e = torch.randint(lo_e, hi_e + 1, (4000,), generator=g0).double()
+    x = (torch.rand(4000, generator=g0, dtype=torch.float64) + 1.0) * torch.pow(torch.tensor(2.0, dtype=torch.float64), e)
+    x = x * torch.where(torch.rand(4000, generator=g0) < 0.5, -1.0, 1.0).double()
+    x = x[x.abs() <= (65504.0 if dtype == torch.float16 else 3.3e38)]
+    ties = []
+    for k in (-3, 0, 5, emin, emin - 3):                     # midpoints of neighbours, and the same a float64 ulp / an fp32 half-ulp off
+        u = 2.0 ** (k - (p - 1)) if k >= emin else 2.0 ** (emin - (p - 1))
+        base = 2.0 ** k if k >= emin else 3 * u
+        for m in (base + 0.5 * u, base + 1.5 * u, base + 0.5 * u * (1 + 2.0 ** -30), base + 1.5 * u * (1 - 2.0 ** -30),
+                  base + 0.5 * u + base * 2.0 ** -52, base + 1.5 * u - base * 2.0 ** -52):
+            ties += [m, -m]
+    x = torch.cat((x, torch.tensor(ties, dtype=torch.float64)))
+    got = R.round_to(x, dtype)
+    assert got.dtype == dtype
+    want = torch.tensor([_rne_rational(float(v), p, emin) for v in x], dtype=torch.float64)
+    assert torch.equal(got.double(), want)
+    assert (got.double() != x).any()
+
+
+def test_round_to_f16_saturates_keeps_nan_and_underflows_gradually():
+    inf, nan = float("inf"), float("nan")
+    x = torch.tensor([65504.0, 65519.9, 65520.0, 65536.0, 1e30, inf, -65519.9, -65520.0, -inf, nan,
+                      2.0 ** -24, 2.0 ** -25, 2.0 ** -25 * (1 + 2.0 ** -40), 1.5 * 2.0 ** -24, 2.5 * 2.0 ** -24, -(2.0 ** -26), 0.0, -0.0,
+                      2049.0, 2051.0, 1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -11], dtype=torch.float64)
+    want = [65504.0, 65504.0, 65504.0, 65504.0, 65504.0, 65504.0, -65504.0, -65504.0, -65504.0, nan,
+            2.0 ** -24, 0.0, 2.0 ** -24, 2.0 ** -23, 2.0 ** -23, -0.0, 0.0, -0.0,
+            2048.0, 2052.0, 1.0, 1.0 + 2.0 ** -9]
+    got = R.round_to(x, torch.float16)
+    assert got.dtype == torch.float16
+    for g, w, v in zip(got.double().tolist(), want, x.tolist()):
+        assert (g != g and w != w) or (g == w and np.signbit(g) == np.signbit(w)), (v, g, w)
+
+
+def test_round_to_bf16_overflows_to_inf_and_is_torchs_conversion_on_fp32_values():
+    inf, nan = float("inf"), float("nan")
+    big = float(torch.tensor(3.3895313892515355e38))          # the largest bf16
+    x = torch.tensor([big, big * (1 + 2.0 ** -10), big * (1 + 2.0 ** -8), 1e300, inf, -inf, nan, 1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8,
+                      2.0 ** -133, 2.0 ** -134, 2.0 ** -134 * 1.0000001, -0.0], dtype=torch.float64)
+    want = [big, big, inf, inf, inf, -inf, nan, 1.0, 1.0 + 2.0 ** -6, 2.0 ** -133, 0.0, 2.0 ** -133, -0.0]
+    for g, w, v in zip(R.round_to(x, torch.bfloat16).double().tolist(), want, x.tolist()):
+        assert (g != g and w != w) or (g == w and np.signbit(g) == np.signbit(w)), (v, g, w)
+    g0 = _gen(12)
+    f = (torch.randn(20000, generator=g0) * torch.exp(torch.empty(20000).uniform_(-80, 80, generator=g0)))
+    f = torch.cat((f, torch.tensor([1.00390625, 1.01171875, inf, -inf, 3.39e38, -3.4e38, 1e-40, -9.2e-41])))   # two ties, overflow, subnormals
+    assert torch.equal(R.round_to(f.double(), torch.bfloat16).view(torch.int16), f.to(torch.bfloat16).view(torch.int16))
+
+
+def test_round_to_f16_agrees_with_the_hi_plane_of_split_planes():
+    """kernel_entries.split_planes is the host mirror of the kernels' split store; its ``hi`` is the same saturating rounding of an
+    fp32 value -- over the whole range, the saturating values and +-inf included"""
+    from plip_amd.kernel_entries import split_planes
+    g0 = _gen(13)
+    f = torch.randn(64, 512, generator=g0) * torch.exp2(torch.randint(-30, 20, (64, 512), generator=g0).float())
+    f[0, :8] = torch.tensor([65504.0, 65519.99, 65520.0, -65520.0, float("inf"), float("-inf"), 5.96e-8, 2.98e-8])
+    hi, _ = split_planes(f, torch.float16)
+    got = R.round_to(f.double(), torch.float16)
+    assert torch.equal(got.view(torch.int16), hi.view(torch.int16))
+    assert (got.abs() == 65504).sum() > 100 and ((got != 0) & (got.abs() < 2.0 ** -14)).sum() > 1000 and (got == 0).sum() > 1000
+
+
+def test_ord16_counts_units_in_the_last_place():
+    for dtype in (torch.float16, torch.bfloat16):
+        t = torch.tensor([-2.0, -1.0, -0.0, 0.0, 1.0], dtype=dtype)
+        o = R.ord16(t)
+        assert o[2] == 0 and o[3] == 0 and (o[1:] >= o[:-1]).all()
+        one = torch.tensor([1.0], dtype=dtype)
+        nxt = (one.view(torch.int16) + 1).view(dtype)
+        assert int(R.ord16(nxt) - R.ord16(one)) == 1 and int(R.ord16(-nxt) - R.ord16(-one)) == -1
+    tiny = torch.tensor([2.0 ** -24, -(2.0 ** -24)], dtype=torch.float16)
+    assert R.ord16(tiny).tolist() == [1, -1]

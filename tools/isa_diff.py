@@ -39,10 +39,11 @@ def disassembly(co):
 
 
 def functions(asm):
-    """-> {symbol: body text}"""
+    """-> {symbol: body text}, without each line's address: a kernel that only MOVED inside its code object (another kernel of the
+    unit grew) is the same kernel -- branches are relative and the encodings stay in the text"""
     out = {}
     for m in re.finditer(r"^[0-9a-f]+ <([^>]+)>:\n(.*?)(?=^[0-9a-f]+ <|\Z)", asm, re.S | re.M):
-        out[m.group(1)] = m.group(2)
+        out[m.group(1)] = re.sub(r"// [0-9A-F]+:", "//", m.group(2))
     return out
 
 
