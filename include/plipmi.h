@@ -286,6 +286,25 @@ int plipmi_tower_shape(plipmi_handle h, int tower, int32_t* shape);
 int plipmi_encode_tower_outputs(plipmi_handle h, int tower, const void* input, const int64_t* attention_mask, int B, int eos_token_id,
                                 float* last_hidden, float* pooled, float* hidden_states, float* attentions, void* stream);
 
+/* Attention summaries -- what the attention probabilities are mostly pulled for, without the [L,B,H,S,S] tensor.  For a tower of L
+ * blocks, H heads and S tokens let P_l[b,h] be block l's S x S probabilities exactly as plipmi_encode_tower_outputs defines them (HF
+ * eager attention, the text tower under causal + padding mask, masked entries exactly 0, a row with no live key all zeros), and r_b
+ * the pooled row of sample b: row 0 (CLS) for vision, the row the eos_token_id rule of plipmi_encode_text picks for text.
+ *   pooled_attention : fp32 [L,B,H,S]  P_l[b,h][r_b, :] -- which tokens the pooled token looked at, the bits `attentions` holds there
+ *   rollout_matrix   : fp32 [B,S,S]    R_L[b], with R_0 = I and R_l = (1/2 A_l + 1/2 I) R_{l-1}, A_l = (1/H) sum_h P_l[b,h] summed in
+ *                                      the order h = 0 .. H-1, the product summed over k = 0 .. S-1, all in fp32: attention rollout
+ *                                      (Abnar & Zuidema 2020) with residual weight 1/2 and head mean.  A dead row i of A_l leaves
+ *                                      1/2 e_i: defined, not an error.  Rows with live keys throughout sum to 1.
+ *   rollout          : fp32 [B,S]      row r_b of R_L[b]
+ * input, attention_mask, eos_token_id and the B <= max_batch rule are those of plipmi_encode_tower_outputs.  Any output may be NULL,
+ * not all of them.  The walk is plipmi_encode_tower_outputs' (eager, every block dense on every token, q/k/v GEMM + attention as two
+ * kernels) with the summary kernels reading each block's qkv activation; the rollout ping-pongs between two [B,S,S] buffers in handle
+ * scratch outside the tower workspace, reserved on first use and freed by plipmi_destroy (a non-NULL rollout_matrix serves as one of
+ * them) -- 2.7 MB per image for ViT-L/14@336 against 511 MB of attentions.  None of the handle's settings change, and the encode
+ * entries return the same bits after it as before. */
+int plipmi_encode_attention_summary(plipmi_handle h, int tower, const void* input, const int64_t* attention_mask, int B, int eos_token_id,
+                                    float* pooled_attention, float* rollout, float* rollout_matrix, void* stream);
+
 /* in-place row-wise x / sqrt(sum x^2), no epsilon (modeling_clip.py:57-65) */
 int plipmi_l2_normalize(plipmi_handle h, float* x, int N, int D, void* stream);
 

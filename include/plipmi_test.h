@@ -118,6 +118,14 @@ int plipmi_probe_loss_grad(plipmi_handle h, const float* X, int N, int D, const 
  * masked entries exactly 0, a row with no live key all 0.  key_mask int64 [B, S] or NULL.  1 <= S <= 1024. */
 int plipmi_attention_probs(int dtype, const void* qkv, float* probs, int B, int S, int H, int causal, const int64_t* key_mask,
                            void* stream);
+/* The summary kernels behind the attention-summary entry of plipmi.h (csrc/attention_summary.hip) on the same qkv, under the same masks:
+ *   out fp32 [B, H, S] = row rows[b] of P[b, h] (rows int32 [B], each in [0, S)) -- the bits plipmi_attention_probs writes there;
+ *   R_out fp32 [B, S, S] = (1/2 mean_h P[b, h] + 1/2 I) . R_in[b], all fp32, head sum in the order h = 0 .. H-1, product summed over
+ *   k = 0 .. S-1; R_in == NULL: the identity (the bits an explicit identity gives).  R_out must not be R_in.  B <= 65535. */
+int plipmi_attention_pooled_rows(int dtype, const void* qkv, const int32_t* rows, float* out, int B, int S, int H, int causal,
+                                 const int64_t* key_mask, void* stream);
+int plipmi_attention_rollout_step(int dtype, const void* qkv, const float* R_in, float* R_out, int B, int S, int H, int causal,
+                                  const int64_t* key_mask, void* stream);
 /* y [rows, D] (y_dtype, contiguous) = LayerNorm(x[r * x_row_stride : + D]) * g + b.  D % 4 == 0, D <= 2048, x_row_stride % 4 == 0 and
  * >= D, x 16-byte aligned.  y may be x itself for fp32 rows of stride D. */
 int plipmi_layernorm(const float* x, size_t x_row_stride, const float* g, const float* b, void* y, int y_dtype, int rows, int D,

@@ -75,6 +75,8 @@ TEST_SYMBOLS = {
     "plipmi_resample_pos": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "plipmi_probe_loss_grad": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "plipmi_attention_probs": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "plipmi_attention_pooled_rows": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "plipmi_attention_rollout_step": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "plipmi_layernorm": (_i, [_vp, C.c_size_t, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "plipmi_layernorm_emit": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "plipmi_fold_ln": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
@@ -117,6 +119,7 @@ SYMBOLS = {
     "plipmi_set_text_packing": (_i, [_vp, _i]),
     "plipmi_tower_shape": (_i, [_vp, _i, C.POINTER(C.c_int32)]),
     "plipmi_encode_tower_outputs": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "plipmi_encode_attention_summary": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "plipmi_probe_fit": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _f, _i, _f, _vp, C.POINTER(ProbeInfo), _vp]),
     "plipmi_probe_predict": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "plipmi_profile_enable": (_i, [_vp, _i]),

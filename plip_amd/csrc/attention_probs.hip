@@ -14,15 +14,13 @@
 //     (each wave store covers 256 contiguous bytes of the row).
 // Masking follows HF: causal (text), key padding from the attention mask (text), none for vision.  Every masked entry is
 // exp(-inf) = exactly 0.0; a row with no live key at all (HF: NaN) is written as zeros.
-#include "kernels.h"
+#include "attention_probs_dev.h"
 
 namespace plipmi {
 
 namespace {
 
-constexpr int kDh = 64;        // head dim (every CLIP / PLIP variant)
-constexpr int kRows = 16;      // query rows per workgroup
-constexpr int kThreads = 256;  // four waves
+using namespace probs_dev;   // kDh, kRows, kThreads and the two phases (shared with attention_summary.hip)
 
 template <typename T>
 __global__ __launch_bounds__(kThreads) void attention_probs_kernel(const T* __restrict__ qkv, float* __restrict__ probs, int S, int H,
@@ -38,57 +36,18 @@ __global__ __launch_bounds__(kThreads) void attention_probs_kernel(const T* __re
   const T* base = qkv + (size_t)b * S * ld + h * kDh;
 
   // q rows of the block -> LDS (rows past S: zeros, never stored)
-  for (int e = tid; e < kRows * (kDh / 4); e += kThreads) {
-    const int r = e / (kDh / 4), d = (e - r * (kDh / 4)) * 4;
-    const float4 v = r < rows ? load4(base + (size_t)(i0 + r) * ld + d) : make_float4(0.f, 0.f, 0.f, 0.f);
-    *reinterpret_cast<float4*>(&qs[r * kDh + d]) = v;
-  }
+  stage_q<T, kRows>(qs, base, ld, i0, rows, tid);
   __syncthreads();
 
-  // phase 1: scores of every (row, key) of the block
-  const int last_row = i0 + rows - 1;
-  const int nkeys = causal ? min(S, last_row + 1) : S;   // keys any row of the block may attend to
-  for (int j = tid; j < S; j += kThreads) {
-    float acc[kRows];
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) acc[r] = 0.f;
-    const bool live = j < nkeys && (key_mask == nullptr || key_mask[(size_t)b * S + j] != 0);
-    if (live) {
-      const T* kr = base + (size_t)j * ld + D;
-#pragma unroll 4
-      for (int d = 0; d < kDh; d += 4) {
-        const float4 kv = load4(kr + d);
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-          const float4 qv = *reinterpret_cast<const float4*>(&qs[r * kDh + d]);
-          acc[r] = fmaf(qv.x, kv.x, acc[r]);
-          acc[r] = fmaf(qv.y, kv.y, acc[r]);
-          acc[r] = fmaf(qv.z, kv.z, acc[r]);
-          acc[r] = fmaf(qv.w, kv.w, acc[r]);
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) sc[r * S + j] = (live && (!causal || j <= i0 + r)) ? acc[r] : -INFINITY;
-  }
+  // phase 1: scores of every (row, key) of the block, one key per lane
+  score_tile<T, kRows, kRows>(qs, sc, base, ld, D, S, i0, rows, b, causal, key_mask, tid);
   __syncthreads();
 
   // phase 2: one wave per row -- softmax statistics, then the normalised row
   const int lane = tid & 63, wave = tid >> 6;
   for (int r = wave; r < rows; r += kThreads / 64) {
-    const float* sr = sc + r * S;
-    float m = -INFINITY;
-    for (int j = lane; j < S; j += 64) m = fmaxf(m, sr[j]);
-    m = wave_max(m);
     float* pr = probs + (((size_t)b * H + h) * S + (i0 + r)) * S;
-    if (m == -INFINITY) {                 // no live key in this row
-      for (int j = lane; j < S; j += 64) pr[j] = 0.f;
-      continue;
-    }
-    float l = 0.f;
-    for (int j = lane; j < S; j += 64) l += expf(sr[j] - m);
-    const float inv = 1.0f / wave_sum(l);
-    for (int j = lane; j < S; j += 64) pr[j] = expf(sr[j] - m) * inv;
+    softmax_row(sc + r * S, S, lane, [pr](int j, float p) { pr[j] = p; });
   }
 }
 

@@ -271,6 +271,9 @@ struct plipmi_engine {
   plipmi::Buffer bad_id_mem{plipmi::Buffer::kPinnedMapped};
   int* bad_id = nullptr;
   plipmi::Buffer sim_ws;        // plipmi_similarity_topk scratch (allocated on first use, grown on demand)
+  // plipmi_encode_attention_summary scratch: the pooled-row indices and the rollout's two [B, S, S] buffers (allocated on first
+  // use, grown on demand; never part of the tower workspace)
+  plipmi::Buffer summary_ws;
   // linear-probe scratch (plipmi_probe_fit / _predict / _loss_grad): device partials + results, and a pinned host mirror of the
   // trial point, gradient and losses.  Allocations of their own, grown on demand: never part of the tower workspace.
   plipmi::Buffer probe_ws, probe_host{plipmi::Buffer::kPinned};

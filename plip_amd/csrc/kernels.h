@@ -129,6 +129,24 @@ hipError_t launch_attention(const void* qkv, void* out, int dtype, int B, int S,
 hipError_t launch_attention_probs(const void* qkv, float* probs, int dtype, int B, int S, int H, int causal, const int64_t* key_mask,
                                   hipStream_t s);
 
+// rows [B] int32 = the row of each sample that the heads pool: 0 (ids == nullptr, CLS) or the caption's EOS row by the rule of
+// launch_pool_layernorm / launch_pool_gather (kernels.hip eos_position)
+hipError_t launch_pooled_row_index(const int64_t* ids, int S, int eos_id, int* rows, int B, hipStream_t s);
+
+// Attention summaries (attention_summary.hip, plipmi_encode_attention_summary only), from the same qkv buffer and under the same
+// causal / key_mask rules as launch_attention_probs, whose probabilities they reproduce bit for bit.  S <= 1024.
+//   pooled rows:  out fp32 [B, H, S] = row rows[b] of P[b, h]
+//   rollout step: R_out [B, S, S] = (1/2 mean_h P[b, h] + 1/2 I) . R_in[b] in fp32 (head sum h = 0 .. H-1, product k = 0 .. S-1);
+//                 R_in == nullptr: the identity.  R_out must not be R_in.  Dynamic LDS: attention_rollout_lds_bytes(S).
+//                 pooled_out != nullptr (with rows): the step also stores the pooled rows, [B, H, S], the bits of the kernel above
+//   rollout row:  out [B, S] = row rows[b] of R[b]
+size_t attention_rollout_lds_bytes(int S);
+hipError_t launch_attention_pooled_rows(const void* qkv, const int* rows, float* out, int dtype, int B, int S, int H, int causal,
+                                        const int64_t* key_mask, hipStream_t s);
+hipError_t launch_attention_rollout_step(const void* qkv, const float* R_in, float* R_out, int dtype, int B, int S, int H, int causal,
+                                         const int64_t* key_mask, hipStream_t s, const int* rows = nullptr, float* pooled_out = nullptr);
+hipError_t launch_attention_rollout_row(const float* R, const int* rows, float* out, int B, int S, hipStream_t s);
+
 // Linear-probe head (probe.hip): one loss-and-gradient evaluation of the K one-vs-rest logistic problems at WB [K, D + 1] (weights,
 // then intercept) over X [N, D] fp32 with int32 labels y: problem k's positive label is class_base + k, its sample weights pos_w[k] /
 // neg_w[k].  `scratch` (probe_scratch_bytes) holds the per-workgroup partials and the results: *grad = fp32 [K, D + 1], *loss =

@@ -1254,4 +1254,20 @@ hipError_t launch_scale_copy(const float* src, float* dst, int n, float scale, h
   return hipGetLastError();
 }
 
+// rows[b] = the row of sample b that the heads pool (0 when ids == nullptr, else the caption's EOS row): one wavefront per sample
+__global__ __launch_bounds__(256) void pooled_row_index_kernel(const int64_t* __restrict__ ids, int S, int eos_id, int* __restrict__ rows,
+                                                               int B) {
+  const int lane = threadIdx.x & 63;
+  const int smp = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (smp >= B) return;
+  const int pos = ids ? eos_position(ids + (size_t)smp * S, S, eos_id, lane) : 0;
+  if (lane == 0) rows[smp] = pos;
+}
+hipError_t launch_pooled_row_index(const int64_t* ids, int S, int eos_id, int* rows, int B, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  if (S <= 0 || !rows) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pooled_row_index_kernel, dim3((B + 3) / 4), dim3(256), 0, s, ids, S, eos_id, rows, B);
+  return hipGetLastError();
+}
+
 }  // namespace plipmi

@@ -165,6 +165,23 @@ int plipmi_attention_probs(int dtype, const void* qkv, float* probs, int B, int 
   if (e != hipSuccess) return fail(PLIPMI_ERR_HIP, "attention probabilities launch (S=%d) failed: %s", S, hipGetErrorString(e));
   return PLIPMI_OK;
 }
+int plipmi_attention_pooled_rows(int dtype, const void* qkv, const int32_t* rows, float* out, int B, int S, int H, int causal,
+                                 const int64_t* key_mask, void* stream) {
+  if (!valid_dtype(dtype) || !qkv || !rows || !out || B < 0 || B > 65535 || S <= 0 || S > 1024 || H <= 0)
+    return fail(PLIPMI_ERR_INVALID, "bad argument (qkv, rows, out non-null, B <= 65535, 1 <= S <= 1024, H >= 1)");
+  const hipError_t e = launch_attention_pooled_rows(qkv, rows, out, dtype, B, S, H, causal, key_mask, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(PLIPMI_ERR_HIP, "pooled attention rows launch (S=%d) failed: %s", S, hipGetErrorString(e));
+  return PLIPMI_OK;
+}
+int plipmi_attention_rollout_step(int dtype, const void* qkv, const float* R_in, float* R_out, int B, int S, int H, int causal,
+                                  const int64_t* key_mask, void* stream) {
+  if (!valid_dtype(dtype) || !qkv || !R_out || B < 0 || B > 65535 || S <= 0 || S > 1024 || H <= 0)
+    return fail(PLIPMI_ERR_INVALID, "bad argument (qkv, R_out non-null, B <= 65535, 1 <= S <= 1024, H >= 1)");
+  if (R_in == R_out) return fail(PLIPMI_ERR_INVALID, "R_out must not be R_in: every tile of a step reads all of R_in");
+  const hipError_t e = launch_attention_rollout_step(qkv, R_in, R_out, dtype, B, S, H, causal, key_mask, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(PLIPMI_ERR_HIP, "attention rollout step launch (S=%d) failed: %s", S, hipGetErrorString(e));
+  return PLIPMI_OK;
+}
 int plipmi_layernorm(const float* x, size_t x_row_stride, const float* g, const float* b, void* y, int y_dtype, int rows, int D,
                      float eps, void* stream) {
   if (!x || !g || !b || !y || rows < 0 || !valid_dtype(y_dtype)) return fail(PLIPMI_ERR_INVALID, "bad argument");

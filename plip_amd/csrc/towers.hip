@@ -13,10 +13,17 @@ struct LnArgs {         // the LayerNorm side of a folded GEMM (gemm.h EPI_*_LN 
   void* xb_out = nullptr; float* st_out = nullptr; void* lo_io = nullptr;     // producer (lo_io: EPI_RESID_SPLIT's lo plane)
   int planes_other = 0;                                                         // producer: write the planes in the other 16-bit format
 };
-// plipmi_encode_tower_outputs: what run_layers hands out per block (fp32, the call's B samples; nullptr = not asked for)
+// plipmi_encode_tower_outputs / plipmi_encode_attention_summary: what run_layers hands out per block (fp32, the call's B samples;
+// nullptr = not asked for)
 struct Taps {
   float* hidden = nullptr;   // [L+1, B, S, D]: slot l+1 after block l (slot 0, the embeddings, is the caller's)
   float* probs = nullptr;    // [L, B, H, S, S]: block l's attention probabilities (attention_probs.hip)
+  // attention_summary.hip: the pooled query row of every head, and the rollout R_l = (1/2 mean_h P_l + 1/2 I) R_{l-1} ping-ponged
+  // between two buffers (block l writes rollout[l & 1] and reads the other one; block 0 reads the identity)
+  float* pooled_rows = nullptr;             // [L, B, H, S]
+  float* rollout[2] = {nullptr, nullptr};   // [B, S, S] each
+  const int* row_idx = nullptr;             // [B]: the pooled row of each sample (launch_pooled_row_index)
+  bool attention() const { return probs || pooled_rows || rollout[0]; }   // something reads the block's qkv activation
 };
 
 // One tower forward being enqueued: B samples on stream s.
@@ -110,13 +117,28 @@ int enter_block(Forward& f, int l) {
   return PLIPMI_OK;
 }
 
-// Attention of the block whose q/k/v GEMM just wrote t.qkv -> t.att; probs != nullptr: its probabilities first (unpacked rows only)
-int run_attention(Forward& f, float* probs) {
+// Attention of the block whose q/k/v GEMM just wrote t.qkv -> t.att; tap >= 0: block `tap`'s probabilities and / or their summaries
+// first, as the call's Taps ask (unpacked rows only)
+int run_attention(Forward& f, int tap) {
   const Tower& t = f.t;
   const int H = f.m.H, S = t.S, B = f.B;
-  if (probs) {
+  const Taps* taps = tap >= 0 ? f.taps : nullptr;
+  if (taps && taps->probs) {
     Scope sc(f.e, f.s, "attention_probs", 2.0 * B * H * (double)S * S * 64, (double)B * H * S * S * 4);
-    HIP_TRY(launch_attention_probs(t.qkv, probs, f.cur, B, S, H, f.causal, f.key_mask, f.s));
+    HIP_TRY(launch_attention_probs(t.qkv, taps->probs + (size_t)tap * B * H * S * S, f.cur, B, S, H, f.causal, f.key_mask, f.s));
+  }
+  // (with a rollout in the same call, its step stores the pooled rows on its way: the tile that holds them forms them anyway)
+  if (taps && taps->pooled_rows && !taps->rollout[0]) {
+    Scope sc(f.e, f.s, "attention_pooled_rows", 2.0 * B * H * (double)S * 64, (double)B * H * S * (4 + 2.0 * 64 * f.md.esz));
+    HIP_TRY(launch_attention_pooled_rows(t.qkv, taps->row_idx, taps->pooled_rows + (size_t)tap * B * H * S, f.cur, B, S, H, f.causal,
+                                         f.key_mask, f.s));
+  }
+  if (taps && taps->rollout[0]) {
+    Scope sc(f.e, f.s, "attention_rollout_step", 2.0 * B * H * (double)S * S * 64 + 2.0 * B * (double)S * S * S,
+             (double)B * S * (2.0 * H * 64 * f.md.esz + 8.0 * S));
+    HIP_TRY(launch_attention_rollout_step(t.qkv, tap == 0 ? nullptr : taps->rollout[(tap - 1) & 1], taps->rollout[tap & 1], f.cur, B, S, H,
+                                          f.causal, f.key_mask, f.s, taps->row_idx,
+                                          taps->pooled_rows ? taps->pooled_rows + (size_t)tap * B * H * S : nullptr));
   }
   const int impl = f.attn_impl();
   Scope sc(f.e, f.s, impl ? "attention_mfma" : "attention_valu", 4.0 * B * H * (double)S * S * 64, (double)f.M() * 4 * f.m.D * f.md.esz);
@@ -127,27 +149,26 @@ int run_attention(Forward& f, float* probs) {
 // LayerNorm-folded q/k/v projection + attention of one block: ONE kernel where the sequence fits the fused tile (77-token
 // captions: qkv_attention.hip, the `qkv` activation never reaches memory), else the GEMM and the attention kernel.
 // Either way t.att holds the attention output afterwards, the same bits.
-int run_qkv_attention(Forward& f, const LayerW& w, const LnArgs& use, float* probs = nullptr) {
+int run_qkv_attention(Forward& f, const LayerW& w, const LnArgs& use, int tap = -1) {
   Tower& t = f.t;
   const int M = f.M(), D = f.m.D, H = f.m.H, B = f.B;
-  if (!probs && g_fuse_qkv_attention && f.attn_impl() == 1 && !f.packed && !f.small && qkv_attention_supports(f.cur, B, t.S, H, D) &&
+  if (tap < 0 && g_fuse_qkv_attention && f.attn_impl() == 1 && !f.packed && !f.small && qkv_attention_supports(f.cur, B, t.S, H, D) &&
       (g_fuse_qkv_attention == 2 || qkv_attention_pays(B, H, gemm_num_cus()))) {
     Scope sc(f.e, f.s, "qkv_attention", 2.0 * M * 3.0 * D * (double)D + 4.0 * B * H * (double)t.S * t.S * 64, ((double)M * D * 2 + 3.0 * D * D) * f.md.esz);
     HIP_TRY(launch_qkv_attention(f.cur, t.h, w.wqkv, w.bqkv, use.stats, use.inv_d, use.eps, t.att, B, t.S, H, f.causal, f.key_mask, f.s));
     return PLIPMI_OK;
   }
   RUN(run_gemm(f, EPI_BIAS_LN, t.h, w.wqkv, t.qkv, w.bqkv, M, 3 * D, D, 3 * D, 0, "qkv", &use, f.m_dev()));
-  return run_attention(f, probs);
+  return run_attention(f, tap);
 }
 
 // n_layers pre-LN residual blocks over the tower's residual stream x (CLIPEncoderLayer, modeling_clip.py:362-383)
 int run_layers(Forward& f, int n_layers, bool more_follow = false) {
   plipmi_engine* e = f.e;
   Tower& t = f.t;
-  const int M = f.M(), D = f.m.D, F = f.m.F, B = f.B;
+  const int M = f.M(), D = f.m.D, F = f.m.F;
   hipStream_t s = f.s;
-  const size_t probs_per_layer = (size_t)B * f.m.H * t.S * t.S;
-  auto probs_of = [&](int l) -> float* { return f.taps && f.taps->probs ? f.taps->probs + (size_t)l * probs_per_layer : nullptr; };
+  auto tap_of = [&](int l) { return f.taps && f.taps->attention() ? l : -1; };
   auto hidden_of = [&](int l) -> float* { return f.taps && f.taps->hidden ? f.taps->hidden + (size_t)(l + 1) * M * D : nullptr; };
   const float eps = f.md.cfg.layer_norm_eps;
   const int* md = f.m_dev();
@@ -162,7 +183,7 @@ int run_layers(Forward& f, int n_layers, bool more_follow = false) {
     for (int l = 0; l < n_layers; ++l) {
       const LayerW& w = f.m.layers[l];
       RUN(enter_block(f, l));
-      RUN(run_qkv_attention(f, w, use, probs_of(l)));
+      RUN(run_qkv_attention(f, w, use, tap_of(l)));
       RUN(run_gemm(f, EPI_RESID_SPLIT, t.att, w.wo, nullptr, w.bo, M, D, D, D, 0, "out_proj", &emit, md));
       RUN(run_gemm(f, EPI_QGELU_LN, t.h, w.w1, t.mlp, w.b1, M, F, D, F, 0, "fc1", &use, md));
       // a block whose successor runs on the other 16-bit operand type (the last f16 block of a mixed text tower) writes its
@@ -191,7 +212,7 @@ int run_layers(Forward& f, int n_layers, bool more_follow = false) {
     { Scope sc(e, s, "layernorm", 0, (double)M * D * (4 + f.md.esz));
       HIP_TRY(launch_layernorm(t.x, D, w.ln1w, w.ln1b, t.h, f.cur, M, D, eps, s)); }
     RUN(run_gemm(f, EPI_BIAS, t.h, w.wqkv, t.qkv, w.bqkv, M, 3 * D, D, 3 * D, 0, "qkv"));
-    RUN(run_attention(f, probs_of(l)));
+    RUN(run_attention(f, tap_of(l)));
     RUN(run_gemm(f, EPI_BIAS_RESID, t.att, w.wo, t.x, w.bo, M, D, D, D, 0, "out_proj"));
     { Scope sc(e, s, "layernorm", 0, (double)M * D * (4 + f.md.esz));
       HIP_TRY(launch_layernorm(t.x, D, w.ln2w, w.ln2b, t.h, f.cur, M, D, eps, s)); }
@@ -477,6 +498,51 @@ int plipmi_encode_tower_outputs(plipmi_handle h, int tower, const void* input, c
   if (pooled) {
     Scope sc(h, s, "pool_layernorm", 0, (double)B * D * 8);
     HIP_TRY(launch_pool_layernorm(t.x, t.S, D, ids, vision ? -1 : eos_token_id, f.m.head_ln_w, f.m.head_ln_b, eps, pooled, B, s));
+  }
+  return PLIPMI_OK;
+}
+
+// The attention summaries of one tower (include/plipmi.h): the walk of plipmi_encode_tower_outputs -- eager, every block dense on every
+// token, q/k/v GEMM + attention as two kernels -- with the summary kernels (attention_summary.hip) tapping each block's qkv activation.
+// The pooled-row indices and the rollout's ping-pong buffers live in handle scratch of their own (summary_ws), outside the tower
+// workspace; a caller's rollout_matrix serves as the buffer the last block writes.
+int plipmi_encode_attention_summary(plipmi_handle h, int tower, const void* input, const int64_t* attention_mask, int B, int eos_token_id,
+                                    float* pooled_attention, float* rollout, float* rollout_matrix, void* stream) {
+  RUN(check_batch(h, B));
+  if (!valid_tower(tower)) return fail(PLIPMI_ERR_INVALID, "tower must be 0 (vision) or 1 (text), got %d", tower);
+  const bool vision = tower == PLIPMI_VISION;
+  if (!vision) RUN(check_async(h));
+  if (B == 0) return PLIPMI_OK;
+  if (!input) return fail(PLIPMI_ERR_INVALID, "null input");
+  if (!pooled_attention && !rollout && !rollout_matrix) return fail(PLIPMI_ERR_INVALID, "no output buffer given");
+  if (vision && attention_mask) return fail(PLIPMI_ERR_INVALID, "the vision tower takes no attention mask");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Forward f(h, tower, B, attention_mask, s, Forward::kEveryToken, /*may_pack=*/false);
+  const int S = f.t.S, L = f.m.L;
+  const bool roll = rollout || rollout_matrix;
+  // scratch: rows [B] int32, then the rollout buffers the caller did not bring (one beside a rollout_matrix, else two)
+  const size_t rows_bytes = align_up((size_t)B * sizeof(int), 256), r_bytes = align_up((size_t)B * S * S * sizeof(float), 256);
+  const int own = roll ? (rollout_matrix ? 1 : 2) : 0;
+  RUN(h->summary_ws.reserve(rows_bytes + own * r_bytes, s));
+  int* rows = reinterpret_cast<int*>(h->summary_ws.data());
+  float* r0 = reinterpret_cast<float*>(h->summary_ws.data() + rows_bytes);
+  Taps taps;
+  taps.pooled_rows = pooled_attention;
+  taps.row_idx = rows;
+  if (roll) {
+    const int last = (L - 1) & 1;               // the buffer block L-1 writes
+    taps.rollout[last] = rollout_matrix ? rollout_matrix : r0 + r_bytes / sizeof(float);
+    taps.rollout[last ^ 1] = r0;
+  }
+  f.taps = &taps;
+  const int64_t* ids = vision ? nullptr : reinterpret_cast<const int64_t*>(input);
+  { Scope sc(h, s, "pooled_row_index", 0, (double)B * (vision ? 4 : S * 8));
+    HIP_TRY(launch_pooled_row_index(ids, S, vision ? -1 : eos_token_id, rows, B, s)); }
+  RUN(embed(f, input, false, -1));
+  RUN(run_layers(f, L));
+  if (rollout) {
+    Scope sc(h, s, "attention_rollout_row", 0, (double)B * S * 8);
+    HIP_TRY(launch_attention_rollout_row(taps.rollout[(L - 1) & 1], rows, rollout, B, S, s));
   }
   return PLIPMI_OK;
 }

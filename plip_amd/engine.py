@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from .config import PlipConfig
-from .outputs import TowerOutput, tower_output_bytes
+from .outputs import AttentionSummary, TowerOutput, attention_summary_bytes, tower_output_bytes
 
 _DTYPES = {"fp32": _lib.F32, "f32": _lib.F32, "float32": _lib.F32, torch.float32: _lib.F32,
            "bf16": _lib.BF16, "bfloat16": _lib.BF16, torch.bfloat16: _lib.BF16,
@@ -813,6 +813,65 @@ class Engine:
         return TowerOutput(last_hidden_state=last, pooler_output=pooled,
                            hidden_states=None if hs is None else tuple(hs.unbind(0)),
                            attentions=None if att is None else tuple(att.unbind(0)))
+
+    def _tower_input_check(self, code: int, inp: torch.Tensor, attention_mask) -> None:
+        """the input checks ``tower_outputs`` and ``attention_summary`` share"""
+        cfg = self.cfg
+        if code == _lib.VISION:
+            if attention_mask is not None:
+                raise ValueError("the vision tower takes no attention_mask")
+            ih, iw = self.image_hw
+            if inp.dim() != 4 or tuple(inp.shape[1:]) != (3, ih, iw):
+                raise ValueError(f"Input image size ({tuple(inp.shape)}) doesn't match model ([B,3,{ih},{iw}]).")
+        elif inp.dim() != 2 or inp.shape[1] != cfg.context_length:
+            raise ValueError(f"input_ids must be [B,{cfg.context_length}], got {tuple(inp.shape)}")
+        elif inp.device.type == "cpu" and inp.numel() and (int(inp.min()) < 0 or int(inp.max()) >= cfg.vocab_size):
+            raise IndexError(f"token id out of range [0,{cfg.vocab_size})")
+
+    def attention_summary(self, tower: str, inp: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                          pooled_attention: bool = True, rollout: bool = True, rollout_matrix: bool = False,
+                          eos_token_id: Optional[int] = None) -> AttentionSummary:
+        """What attention maps are mostly pulled for, without the [L,B,H,S,S] tensor (include/plipmi.h plipmi_encode_attention_summary):
+        ``pooled_attention`` -- L tensors [B,H,S], the pooled query row (CLS; the caption's EOS row) of every head, the bits
+        ``tower_outputs(..., output_attentions=True).attentions`` holds there --, ``rollout`` [B,S] -- the pooled row of the attention
+        rollout (residual weight 1/2, head mean) -- and ``rollout_matrix`` [B,S,S], the whole rollout; fp32 on the GPU.  Inputs as
+        ``tower_outputs``; runs in chunks of ``max_batch`` samples on this engine.  Raises ValueError before allocating anything when
+        outputs and scratch would not fit the device's free memory."""
+        code = _tower_code(tower)
+        vision = code == _lib.VISION
+        self._tower_input_check(code, inp, attention_mask)
+        if not (pooled_attention or rollout or rollout_matrix):
+            raise ValueError("attention_summary: nothing asked for (pooled_attention, rollout and rollout_matrix are all off)")
+        S, D, H, L = self.tower_shape(tower)
+        B = int(inp.shape[0])
+        chunks = list(self._chunks(B))
+        nb = attention_summary_bytes(B, S, H, L, pooled_attention, rollout, rollout_matrix)
+        per_chunk = attention_summary_bytes(min(B, self.max_batch), S, H, L, pooled_attention, rollout, rollout_matrix)
+        need = nb["pooled_attention"] + nb["rollout"] + nb["rollout_matrix"] + per_chunk["scratch"] + \
+            (per_chunk["pooled_attention"] if len(chunks) > 1 else 0)
+        free, _ = torch.cuda.mem_get_info(self.device)
+        if need > free:
+            raise ValueError(f"{tower} attention summary for {B} samples needs {need / 2**20:.0f} MiB of device memory, "
+                             f"{free / 2**20:.0f} MiB are free: pass fewer samples or drop rollout_matrix")
+        eos = self.cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
+        dev = dict(device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            x = inp.to(device=self.device, dtype=torch.float32 if vision else torch.int64).contiguous()
+            mask = None if attention_mask is None else attention_mask.to(device=self.device, dtype=torch.int64).contiguous()
+            pa = torch.empty((L, B, H, S), **dev) if pooled_attention else None
+            ro = torch.empty((B, S), **dev) if rollout else None
+            rm = torch.empty((B, S, S), **dev) if rollout_matrix else None
+            for a, b in chunks:
+                one = len(chunks) == 1
+                pa_c = None if pa is None else (pa if one else torch.empty((L, b - a, H, S), **dev))
+                _lib.check(self.lib.plipmi_encode_attention_summary(
+                    self._h, code, _ptr(x[a:b]), _ptr(None if mask is None else mask[a:b]), b - a, eos, _ptr(pa_c),
+                    _ptr(None if ro is None else ro[a:b]), _ptr(None if rm is None else rm[a:b]), self._stream()),
+                    "plipmi_encode_attention_summary")
+                if not one and pa is not None:
+                    pa[:, a:b].copy_(pa_c)
+                    del pa_c
+        return AttentionSummary(pooled_attention=None if pa is None else tuple(pa.unbind(0)), rollout=ro, rollout_matrix=rm)
 
     def hidden(self, tower: str, layer: int, inp: torch.Tensor) -> torch.Tensor:
         """HF ``hidden_states[layer]`` of a tower (parity tests)."""

@@ -259,6 +259,34 @@ def attention_probs(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool = Fa
     return probs
 
 
+def attention_pooled_rows(qkv: torch.Tensor, rows: torch.Tensor, B: int, S: int, H: int, causal: bool = False,
+                          key_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``plipmi_attention_pooled_rows``: row ``rows[b]`` (int32 [B]) of every head's probabilities -> fp32 [B, H, S]."""
+    lib = _lib.load()
+    assert qkv.is_cuda and qkv.is_contiguous() and qkv.shape == (B * S, 3 * H * 64)
+    assert rows.is_cuda and rows.dtype == torch.int32 and rows.is_contiguous() and rows.shape == (B,)
+    assert key_mask is None or (key_mask.is_cuda and key_mask.dtype == torch.int64 and key_mask.is_contiguous() and key_mask.shape == (B, S))
+    out = torch.empty((B, H, S) if S <= 1024 else (1,), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _lib.check(lib.plipmi_attention_pooled_rows(_code(qkv.dtype), _ptr(qkv), _ptr(rows), _ptr(out), B, S, H, int(causal), _ptr(key_mask),
+                                                    _stream(qkv)), "plipmi_attention_pooled_rows")
+    return out
+
+
+def attention_rollout_step(qkv: torch.Tensor, R_in: Optional[torch.Tensor], B: int, S: int, H: int, causal: bool = False,
+                           key_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``plipmi_attention_rollout_step``: (1/2 mean_h P + 1/2 I) . R_in -> a new fp32 [B, S, S]; ``R_in`` None = the identity."""
+    lib = _lib.load()
+    assert qkv.is_cuda and qkv.is_contiguous() and qkv.shape == (B * S, 3 * H * 64)
+    assert R_in is None or (R_in.is_cuda and R_in.dtype == torch.float32 and R_in.is_contiguous() and R_in.shape == (B, S, S))
+    assert key_mask is None or (key_mask.is_cuda and key_mask.dtype == torch.int64 and key_mask.is_contiguous() and key_mask.shape == (B, S))
+    out = torch.empty((B, S, S) if S <= 1024 else (1,), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _lib.check(lib.plipmi_attention_rollout_step(_code(qkv.dtype), _ptr(qkv), _ptr(R_in), _ptr(out), B, S, H, int(causal),
+                                                     _ptr(key_mask), _stream(qkv)), "plipmi_attention_rollout_step")
+    return out
+
+
 def layernorm(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: float = 1e-5, out_dtype=torch.float32, inplace: bool = False) -> torch.Tensor:
     """``plipmi_layernorm``: x fp32 [rows, D], possibly a strided view of a wider buffer (row stride and storage offset multiples of 4
     elements, unit column stride) -> contiguous [rows, D] of ``out_dtype``; ``inplace``: y is x itself (contiguous fp32 rows)."""

@@ -24,7 +24,7 @@ import torch
 from . import weights as W
 from .config import PlipConfig, get_config
 from .engine import Engine
-from .outputs import TowerOutput
+from .outputs import AttentionSummary, TowerOutput
 
 
 @dataclass
@@ -58,6 +58,13 @@ class _Tower:
         return self._model._vision_outputs(*args, **kw) if self._vision else self._model._text_outputs(*args, **kw)
 
     __call__ = forward
+
+    @torch.no_grad()
+    def attention_summary(self, *args, **kw) -> AttentionSummary:
+        """``vision_model.attention_summary(pixel_values, interpolate_pos_encoding=False, ...)`` /
+        ``text_model.attention_summary(input_ids, attention_mask=None, ...)``: ``Engine.attention_summary`` of this tower (keywords
+        ``pooled_attention``, ``rollout``, ``rollout_matrix``, ``eos_token_id``)."""
+        return self._model._vision_summary(*args, **kw) if self._vision else self._model._text_summary(*args, **kw)
 
 
 class PlipModel:
@@ -145,6 +152,16 @@ class PlipModel:
             raise ValueError("You have to specify input_ids")
         return self.engine.tower_outputs("text", input_ids, attention_mask, output_hidden_states=bool(output_hidden_states),
                                          output_attentions=bool(output_attentions))
+
+    def _vision_summary(self, pixel_values=None, interpolate_pos_encoding: bool = False, **summary_options) -> AttentionSummary:
+        if pixel_values is None:
+            raise ValueError("You have to specify pixel_values")
+        return self._image_engine(pixel_values, interpolate_pos_encoding).attention_summary("vision", pixel_values, **summary_options)
+
+    def _text_summary(self, input_ids=None, attention_mask=None, **summary_options) -> AttentionSummary:
+        if input_ids is None:
+            raise ValueError("You have to specify input_ids")
+        return self.engine.attention_summary("text", input_ids, attention_mask, **summary_options)
 
     @torch.no_grad()
     def forward(self, input_ids=None, pixel_values=None, attention_mask=None, interpolate_pos_encoding: bool = False,

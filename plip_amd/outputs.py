@@ -1,6 +1,6 @@
 """Per-token tower outputs: the ``BaseModelOutputWithPooling`` of HF ``CLIPVisionTransformer`` / ``CLIPTextTransformer``
 (``last_hidden_state``, ``pooler_output``, ``hidden_states``, ``attentions``) and the buffer arithmetic of
-``plipmi_encode_tower_outputs`` (include/plipmi.h).  No GPU needed here."""
+``plipmi_encode_tower_outputs`` (include/plipmi.h); the attention summaries of ``plipmi_encode_attention_summary``.  No GPU needed here."""
 from __future__ import annotations
 
 from dataclasses import dataclass, fields
@@ -46,3 +46,25 @@ def tower_output_bytes(B: int, S: int, D: int, H: int, L: int, last_hidden: bool
             "pooled": 4 * B * D if pooled else 0,
             "hidden_states": 4 * (L + 1) * B * S * D if hidden_states else 0,
             "attentions": 4 * L * B * H * S * S if attentions else 0}
+
+
+@dataclass
+class AttentionSummary:
+    """``Engine.attention_summary`` (include/plipmi.h plipmi_encode_attention_summary), fp32 on the GPU; a field that was not asked
+    for is None.  ``pooled_attention``: L tensors [B,H,S], the pooled query row (CLS / EOS) of every head's probabilities;
+    ``rollout``: [B,S], the pooled row of the attention rollout; ``rollout_matrix``: [B,S,S], the whole rollout."""
+    pooled_attention: Optional[Tuple[torch.Tensor, ...]] = None
+    rollout: Optional[torch.Tensor] = None
+    rollout_matrix: Optional[torch.Tensor] = None
+
+
+def attention_summary_bytes(B: int, S: int, H: int, L: int, pooled_attention: bool = True, rollout: bool = True,
+                            rollout_matrix: bool = False) -> dict:
+    """fp32 bytes of each buffer ``plipmi_encode_attention_summary`` writes for B samples (0 for one that is not asked for) and of the
+    handle scratch one call of B samples reserves: pooled_attention [L,B,H,S], rollout [B,S], rollout_matrix [B,S,S]; scratch = the
+    rollout's [B,S,S] buffers the caller does not bring (two, one beside a rollout_matrix) plus the row indices."""
+    roll = rollout or rollout_matrix
+    return {"pooled_attention": 4 * L * B * H * S if pooled_attention else 0,
+            "rollout": 4 * B * S if rollout else 0,
+            "rollout_matrix": 4 * B * S * S if rollout_matrix else 0,
+            "scratch": 4 * B + (4 * B * S * S * (1 if rollout_matrix else 2) if roll else 0)}

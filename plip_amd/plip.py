@@ -346,6 +346,39 @@ class PLIP:
             return np.zeros((0, self.model.config.projection_dim), np.float32)
         return torch.cat(outs).detach().cpu().numpy()
 
+    def attention_maps(self, images: Union[List[str], list, np.ndarray, torch.Tensor], batch_size: int, kind: str = "rollout",
+                       image_size: Optional[int] = None) -> np.ndarray:
+        """(extension) One heat-map per image over the patch grid, float32 [N, gh, gw]: ``kind="rollout"`` -- the CLS row of the
+        attention rollout (residual weight 1/2, head mean: include/plipmi.h ``plipmi_encode_attention_summary``) -- or ``"last"`` --
+        the CLS row of the last block's probabilities, averaged over the heads --, the CLS column dropped, reshaped to the grid and
+        NOT renormalised (a map sums to 1 minus the weight CLS keeps on itself).  Runs on the pixels ``encode_images`` encodes for the
+        same ``images`` / ``image_size``, prepared on the host (fp32 pixels; paths are opened, anything that is not a float array goes
+        through ``preprocess_images``); the attention tensor [L,B,H,S,S] is never formed."""
+        if kind not in ("rollout", "last"):
+            raise ValueError(f"kind must be 'rollout' or 'last', got {kind!r}")
+        n_px = self.model.config.image_size if image_size is None else int(image_size)
+        eng = self.model.engine if image_size is None else self.model.engine.at_resolution(n_px, n_px)
+        gh = gw = n_px // self.model.config.patch_size
+        outs = []
+        with torch.no_grad():
+            for s in range(0, len(images), batch_size):
+                chunk = images[s:s + batch_size]
+                if isinstance(chunk, (list, tuple)) and any(isinstance(c, str) for c in chunk):
+                    from PIL import Image
+                    chunk = [Image.open(c) if isinstance(c, str) else c for c in chunk]
+                if torch.is_tensor(chunk) and chunk.dtype != torch.uint8:
+                    px = chunk
+                elif isinstance(chunk, np.ndarray) and chunk.dtype != np.uint8:
+                    px = torch.from_numpy(chunk)
+                else:
+                    px = torch.from_numpy(preprocess_images(list(chunk.cpu().numpy() if torch.is_tensor(chunk) else chunk), n_px, crop=_CROP))
+                out = eng.attention_summary("vision", px, pooled_attention=kind == "last", rollout=kind == "rollout")
+                row = out.rollout if kind == "rollout" else out.pooled_attention[-1].mean(dim=1)
+                outs.append(row[:, 1:].reshape(-1, gh, gw))
+        if not outs:
+            return np.zeros((0, gh, gw), np.float32)
+        return torch.cat(outs).detach().cpu().numpy()
+
     _stage = None            # pinned uint8 [max_batch, n, n, 3] staging rows of the coalescing host loop (allocated on first use)
 
     def _fill_stage(self, tiles, n_px, cap) -> torch.Tensor:
