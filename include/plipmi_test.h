@@ -108,7 +108,7 @@ int plipmi_resample_pos(const float* src, float* dst, int n0, int gh, int gw, in
 int plipmi_probe_loss_grad(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int K, const float* pos_w,
                            const float* neg_w, float alpha, const float* WB, double* loss_out, float* grad_out, void* stream);
 
-/* Kernel-level entries of the kernels AROUND the GEMMs (csrc/kernels.hip, csrc/attention_probs.hip), for tests/test_gpu_small_kernels.py:
+/* Kernel-level entries of the kernels AROUND the GEMMs (csrc/tower_kernels.hip, csrc/head_kernels.hip, csrc/setup_kernels.hip, csrc/attention_probs.hip), for tests/test_gpu_small_kernels.py:
  * each checks its arguments on the host (PLIPMI_ERR_INVALID before any launch), runs the engine's own launcher on `stream` and returns.
  * dtype / y_dtype are PLIPMI_F32 | PLIPMI_BF16 | PLIPMI_F16 (16-bit buffers as raw uint16); "planes" = the split residual form
  * {hi uint16 [rows, D], lo = the blocked 8-bit remainder plane, ((rows + 15) / 16) * 16 * D bytes}; st = fp32 [rows, D / 64, 2]

@@ -9,6 +9,7 @@
 //                               lane, K/V tiles of 64 keys broadcast from LDS, flash-style
 //                               online softmax in chunks of 8 keys.
 //   * attention_mfma_kernel  -- bf16 MFMA kernel (attention_mfma.hip).
+#include "dispatch.h"
 #include "kernels.h"
 
 namespace plipmi {
@@ -131,11 +132,11 @@ hipError_t launch_attention(const void* qkv, void* out, int dtype, int B, int S,
   const dim3 grid(B * H), block(threads);
   // <= 256 threads: the register allocator may use 256 VGPRs (q[64] + acc[64] live); the 1024-thread
   // build (S > 256, e.g. ViT-L/14@336) trades some spills for the larger block.
-#define PLIPMI_ATTN(T, MAXT) \
-  hipLaunchKernelGGL((attention_valu_kernel<T, MAXT>), grid, block, 0, s, (const T*)qkv, (T*)out, S, H, causal, key_mask)
-  if (threads <= 256) { if (dtype == 1) PLIPMI_ATTN(bf16_t, 256); else if (dtype == 2) PLIPMI_ATTN(f16_t, 256); else PLIPMI_ATTN(float, 256); }
-  else                { if (dtype == 1) PLIPMI_ATTN(bf16_t, 1024); else if (dtype == 2) PLIPMI_ATTN(f16_t, 1024); else PLIPMI_ATTN(float, 1024); }
-#undef PLIPMI_ATTN
+  with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    if (threads <= 256) hipLaunchKernelGGL((attention_valu_kernel<T, 256>), grid, block, 0, s, (const T*)qkv, (T*)out, S, H, causal, key_mask);
+    else hipLaunchKernelGGL((attention_valu_kernel<T, 1024>), grid, block, 0, s, (const T*)qkv, (T*)out, S, H, causal, key_mask);
+  });
   return hipGetLastError();
 }
 

@@ -15,6 +15,7 @@
 //                      ds_read_b64_tr_b16 (two [keys][32] images with 64-byte rows -> conflict-free).
 //   Softmax statistics, the running sum and the 1/l normalisation are fp32
 //   (modeling_clip.py:271); P is rounded to the operand type only as the MFMA operand.
+#include "dispatch.h"
 #include "kernels.h"
 
 namespace plipmi {
@@ -472,8 +473,7 @@ static hipError_t launch_attention_mfma_t(const void* qkv, void* out, int B, int
 hipError_t launch_attention_mfma(const void* qkv, void* out, int dtype, int B, int S, int H, int causal, const int64_t* key_mask,
                                  hipStream_t s, const int* cu) {
   if (S <= 0 || (dtype != 1 && dtype != 2)) return hipErrorInvalidValue;
-  return dtype == 1 ? launch_attention_mfma_t<bf16_t>(qkv, out, B, S, H, causal, key_mask, s, cu)
-                    : launch_attention_mfma_t<f16_t>(qkv, out, B, S, H, causal, key_mask, s, cu);
+  return with_half(dtype, [&](auto tag) { return launch_attention_mfma_t<decltype(tag)>(qkv, out, B, S, H, causal, key_mask, s, cu); });
 }
 
 }  // namespace plipmi

@@ -14,6 +14,7 @@
 //     (each wave store covers 256 contiguous bytes of the row).
 // Masking follows HF: causal (text), key padding from the attention mask (text), none for vision.  Every masked entry is
 // exp(-inf) = exactly 0.0; a row with no live key at all (HF: NaN) is written as zeros.
+#include "dispatch.h"
 #include "attention_probs_dev.h"
 
 namespace plipmi {
@@ -61,21 +62,17 @@ hipError_t launch_attention_probs(const void* qkv, float* probs, int dtype, int 
   if (S <= 0 || S > 1024 || H <= 0 || !qkv || !probs) return hipErrorInvalidValue;
   const size_t lds = attention_probs_lds_bytes(S);    // <= 16 x 1088 x 4 = 68 KiB (S = 1024)
   const dim3 grid((S + kRows - 1) / kRows, H, B), block(kThreads);
-#define PLIPMI_PROBS(T)                                                                                                   \
-  do {                                                                                                                    \
-    if (lds > 64 * 1024) {                                                                                                \
-      const hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_probs_kernel<T>),                \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                    \
-      if (e_ != hipSuccess) return e_;                                                                                    \
-    }                                                                                                                     \
-    hipLaunchKernelGGL(attention_probs_kernel<T>, grid, block, lds, s, (const T*)qkv, probs, S, H, causal, key_mask);     \
-  } while (0)
-  if (dtype == 1) PLIPMI_PROBS(bf16_t);
-  else if (dtype == 2) PLIPMI_PROBS(f16_t);
-  else if (dtype == 0) PLIPMI_PROBS(float);
-  else return hipErrorInvalidValue;
-#undef PLIPMI_PROBS
-  return hipGetLastError();
+  if (dtype != 0 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    if (lds > 64 * 1024) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_probs_kernel<T>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(attention_probs_kernel<T>, grid, block, lds, s, (const T*)qkv, probs, S, H, causal, key_mask);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace plipmi

@@ -17,6 +17,7 @@
 //                           holds row rows[b] forms it anyway): the walk then needs no attention_pooled_rows launch.
 //   attention_rollout_row   out [B, S] = row rows[b] of R [B, S, S].
 // All stores are ordinary vector stores; nothing here uses inline assembly.
+#include "dispatch.h"
 #include "attention_probs_dev.h"
 
 namespace plipmi {
@@ -183,20 +184,18 @@ hipError_t launch_attention_pooled_rows(const void* qkv, const int* rows, float*
                                         const int64_t* key_mask, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   if (S <= 0 || S > 1024 || H <= 0 || B > 65535 || !qkv || !rows || !out) return hipErrorInvalidValue;
-  if (dtype == 1) return pooled_rows<bf16_t>(qkv, rows, out, B, S, H, causal, key_mask, s);
-  if (dtype == 2) return pooled_rows<f16_t>(qkv, rows, out, B, S, H, causal, key_mask, s);
-  if (dtype == 0) return pooled_rows<float>(qkv, rows, out, B, S, H, causal, key_mask, s);
-  return hipErrorInvalidValue;
+  if (dtype != 0 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  return with_dtype(dtype, [&](auto tag) { return pooled_rows<decltype(tag)>(qkv, rows, out, B, S, H, causal, key_mask, s); });
 }
 
 hipError_t launch_attention_rollout_step(const void* qkv, const float* R_in, float* R_out, int dtype, int B, int S, int H, int causal,
                                          const int64_t* key_mask, hipStream_t s, const int* rows, float* pooled_out) {
   if (B <= 0) return hipSuccess;
   if (S <= 0 || S > 1024 || H <= 0 || B > 65535 || !qkv || !R_out || R_in == R_out || (pooled_out && !rows)) return hipErrorInvalidValue;
-  if (dtype == 1) return rollout_step<bf16_t>(qkv, R_in, R_out, B, S, H, causal, key_mask, rows, pooled_out, s);
-  if (dtype == 2) return rollout_step<f16_t>(qkv, R_in, R_out, B, S, H, causal, key_mask, rows, pooled_out, s);
-  if (dtype == 0) return rollout_step<float>(qkv, R_in, R_out, B, S, H, causal, key_mask, rows, pooled_out, s);
-  return hipErrorInvalidValue;
+  if (dtype != 0 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  return with_dtype(dtype, [&](auto tag) {
+    return rollout_step<decltype(tag)>(qkv, R_in, R_out, B, S, H, causal, key_mask, rows, pooled_out, s);
+  });
 }
 
 hipError_t launch_attention_rollout_row(const float* R, const int* rows, float* out, int B, int S, hipStream_t s) {

@@ -1,0 +1,19 @@
+// dispatch.h -- host only: a launcher's dtype code (kernels.h: 0 = fp32, 1 = bf16, 2 = f16) turned into the operand type, in one
+// place: with_half(dtype, [&](auto tag) { using H = decltype(tag); hipLaunchKernelGGL(k<H>, ...); }).  Neither function checks the
+// code -- every launcher validates its arguments first, with its own return codes -- so the last arm takes whatever is left: f16
+// for with_half, fp32 for with_dtype.  What the callback returns is returned.
+#pragma once
+#include "common.h"
+
+namespace plipmi {
+
+template <typename F>
+inline decltype(auto) with_half(int dtype, F&& f) {
+  return dtype == 1 ? f(bf16_t{}) : f(f16_t{});
+}
+template <typename F>
+inline decltype(auto) with_dtype(int dtype, F&& f) {
+  return dtype == 1 ? f(bf16_t{}) : dtype == 2 ? f(f16_t{}) : f(float{});
+}
+
+}  // namespace plipmi

@@ -19,6 +19,7 @@
 // its heads at batch 8, plip.py:90-91): the big tiles walk K serially whatever M is (fc2: 48 dependent K tiles = 45 us for
 // 400 rows), this kernel splits it 8 ways.  A row's result never depends on the other rows of ITS call, so embeddings are
 // bit-identical across batch sizes within each of the two regimes; between them they differ by fp32 summation order.
+#include "dispatch.h"
 #include "gemm.h"
 #include "gemm_lds.h"
 
@@ -251,7 +252,7 @@ int gemm_launch_skinny(int dtype, int epi, const GemmParams& p, hipStream_t s, c
        nullptr, "gemm_skinny<f16,32x64_splitk,patch>", "gemm_skinny<f16,32x64_splitk,ln_bias>", "gemm_skinny<f16,32x64_splitk,ln_qgelu>",
        "gemm_skinny<f16,32x64_splitk,resid_emit>", "gemm_skinny<f16,32x64_splitk,resid_split>"}};
   if (kernel_name) *kernel_name = names[dtype - 1][epi];
-  return dtype == 1 ? launch_skinny_epi<bf16_t>(epi, p, s) : launch_skinny_epi<f16_t>(epi, p, s);
+  return with_half(dtype, [&](auto tag) { return launch_skinny_epi<decltype(tag)>(epi, p, s); });
 }
 
 }  // namespace plipmi

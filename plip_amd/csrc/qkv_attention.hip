@@ -21,6 +21,7 @@
 //     path's (tests/test_gpu_attention.py::test_fused_qkv_attention_matches_the_two_kernels).
 #include <mutex>
 
+#include "dispatch.h"
 #include "gemm.h"
 #include "gemm_lds.h"
 #include "kernels.h"
@@ -472,7 +473,7 @@ hipError_t launch_qkv_attention(int dtype, const void* A, const void* W, const f
   QkvAttnParams p;
   p.A = A; p.W = W; p.c2 = c2; p.stats = stats; p.out = out; p.key_mask = key_mask;
   p.B = B; p.S = S; p.H = H; p.D = D; p.causal = causal; p.ln_inv_d = ln_inv_d; p.ln_eps = ln_eps; p.trace = trace;
-  return dtype == 1 ? launch_t<bf16_t>(p, s) : launch_t<f16_t>(p, s);
+  return with_half(dtype, [&](auto tag) { return launch_t<decltype(tag)>(p, s); });
 }
 
 }  // namespace plipmi

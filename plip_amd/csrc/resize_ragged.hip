@@ -1,7 +1,7 @@
 // resize_ragged.hip -- Pillow-exact 8-bit bicubic resize + centre crop of a RAGGED batch: B uint8 RGB images, each with its own
 // height and width, packed end to end in one buffer -> uint8 [B, n, n, 3] tiles for plipmi_encode_image_u8 (reference:
 // reproducibility/embedders/transform.py:45-48, plip.py:32-35 on lists whose sizes differ).  The uniform entry
-// (kernels.hip resize_h_kernel / resize_v_kernel) takes host-built coefficient tables, one pair per image size; here nothing per
+// (head_kernels.hip resize_h_kernel / resize_v_kernel) takes host-built coefficient tables, one pair per image size; here nothing per
 // size is built on the host -- four launches per batch, whatever the sizes:
 //
 //   ragged_plan_kernel   one workgroup: per image the resize geometry (resize_ragged.h rr_geometry), the two axis descriptors and the

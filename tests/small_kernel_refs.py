@@ -1,5 +1,5 @@
 """Shared by tests/test_small_kernel_refs_host.py, tests/test_gpu_small_kernels.py and tests/test_gpu_front_end.py (and tests/test_gpu_gemm.py
-for ``slice_stats``): plain float64 torch restatements of the kernels around the GEMMs (plip_amd/csrc/kernels.hip, attention_probs.hip), written from
+for ``slice_stats``): plain float64 torch restatements of the kernels around the GEMMs (plip_amd/csrc/tower_kernels.hip, head_kernels.hip, setup_kernels.hip, attention_probs.hip), written from
 the operations' definitions and not from the kernels.  Each is checked on the CPU against an independent formulation
 (torch.nn.functional, numpy, oracle/clip_oracle.py) by the host test; the GPU test compares the kernels with them.
 

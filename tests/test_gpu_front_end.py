@@ -82,7 +82,7 @@ def _in_grid(px, P):
 
 
 # =====================================================================================================================================
-# unfold_kernel<vector / scalar>, unfold_u8_kernel (csrc/kernels.hip): a re-index, so exact
+# unfold_kernel<vector / scalar>, unfold_u8_kernel (csrc/tower_kernels.hip): a re-index, so exact
 # =====================================================================================================================================
 UNFOLD_CASES = [(32, 64, 96),      # vector path
                 (16, 52, 72),      # vector path; the grid floors (3 x 4): the remainder pixels must not appear

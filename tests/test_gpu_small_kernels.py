@@ -178,7 +178,7 @@ def test_attention_probs_never_read_dead_key_rows(S, causal, dname):
 
 
 # =====================================================================================================================================
-# LayerNorm family (csrc/kernels.hip)
+# LayerNorm family (csrc/tower_kernels.hip)
 # =====================================================================================================================================
 LN_D = [4, 64, 128, 252, 384, 512, 640, 768, 1024, 1280, 1664, 2048]
 LN_ROWS = [1, 2, 3, 7, 8, 9, 1001]

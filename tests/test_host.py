@@ -451,7 +451,9 @@ def test_named_test_hooks_reject_values_outside_their_range():
 def test_isa_diff_compares_kernels_without_their_addresses():
     """tools/isa_diff.py functions(): a kernel that only moved inside its code object (another kernel of the unit grew) compares
     equal -- the address column is dropped, the encodings and the <symbol+offset> branch targets stay --, one changed instruction
-    or encoding does not"""
+    or encoding does not.  compare(): a kernel that moved to another UNIT is compared with itself and reported as moved; a difference
+    made only of the pc-relative literals after s_getpc_b64 is "constant address only" and not a failure; such a literal plus one
+    real instruction change is a failure"""
     import importlib.util
     spec = importlib.util.spec_from_file_location("isa_diff", os.path.join(ROOT, "tools", "isa_diff.py"))
     mod = importlib.util.module_from_spec(spec)
@@ -468,3 +470,46 @@ def test_isa_diff_compares_kernels_without_their_addresses():
     assert set(a) == {"_Z1kv", "_Z2k2v"} and a == moved and "C0060002" in a["_Z1kv"] and "<_Z1kv+0x4>" in a["_Z1kv"]
     assert mod.functions(listing(0x1900, "v_sub_f32_e32 v1, v0, v0", "04020100"))["_Z1kv"] != a["_Z1kv"]
     assert mod.functions(listing(0x1900, enc="02020101"))["_Z1kv"] != a["_Z1kv"]
+    # the padding up to the next kernel's alignment is not part of a kernel: what follows it decides its form
+    padded = listing(0x1900).replace("\n\n", f"\n\ts_nop 0    // {0x1910:012X}: BF800000\n\t\t...\n\n", 1) + f"\ts_code_end    // {0x1A04:012X}: BF9F0000\n"
+    assert mod.functions(padded) == a
+
+    # compare(): kernels are matched by symbol over all units, and the literals of the s_add_u32 / s_addc_u32 pair directly after
+    # an s_getpc_b64 (the pc-relative address of the unit's constant data) are a class of their own
+    def table_kernel(base, lo="FFFE7218", mul="v_mul_f32_e32 v7, s7, v3", mul_enc="0A0E0607", other_lit="00000010"):
+        return (f"{base:016x} <_Z1tv>:\n"
+                f"\ts_getpc_b64 s[22:23]    // {base:012X}: BE961C00\n"
+                f"\ts_add_u32 s22, s22, 0x{lo.lower()}    // {base + 4:012X}: 8016FF16 {lo}\n"
+                f"\ts_addc_u32 s23, s23, -1    // {base + 12:012X}: 8217FF17 FFFFFFFF\n"
+                f"\ts_add_u32 s2, s2, 0x{other_lit.lstrip('0')}    // {base + 20:012X}: 8002FF02 {other_lit}\n"
+                f"\t{mul}    // {base + 28:012X}: {mul_enc}\n"
+                f"\ts_endpgm    // {base + 32:012X}: BF810000\n")
+    meta = {".vgpr_count": "8", ".sgpr_count": "24", ".private_segment_fixed_size": "0"}
+    metas = {"_Z1kv": meta, "_Z2k2v": meta, "_Z1tv": meta}
+    parent = {"kernels.o": (listing(0x1900) + "\n" + table_kernel(0x1B00), metas), "engine.o": None}
+
+    def run(t_text, t_meta=meta):
+        split = {"tower_kernels.o": (listing(0x0), {"_Z1kv": meta, "_Z2k2v": meta}), "setup_kernels.o": (t_text, {"_Z1tv": t_meta}),
+                 "engine.o": None}
+        lines, bad = mod.compare(parent, split)
+        return "\n".join(lines), bad
+
+    text, bad = run(table_kernel(0x300))                                    # moved to other units, nothing else
+    assert not bad and "tower_kernels.o: 2 kernels, 2 symbols, 2 moved here from kernels.o: identical" in text
+    assert "setup_kernels.o: 1 kernels, 1 symbols, 1 moved here from kernels.o: identical" in text and "engine.o: no device code" in text
+    assert text.splitlines()[-1].startswith("IDENTICAL") and "3 in another unit than before, 0 differ in constant addresses only" in text
+    text, bad = run(table_kernel(0x300, lo="FFFE6E48"))                     # the constant data sits elsewhere: listed, exit status 0
+    assert not bad and "setup_kernels.o: 1 kernels, 1 symbols, 1 moved here from kernels.o: constant address only" in text
+    assert "    constant address only  _Z1tv" in text and "1 differ in constant addresses only" in text
+    text, bad = run(table_kernel(0x300, lo="FFFE6E48", mul="v_mul_f32_e32 v7, s6, v3", mul_enc="0A0E0606"))   # ... plus one real change
+    assert bad and "    code  _Z1tv: 6 -> 6 instructions" in text and "constant address only" not in text.replace("constant addresses only", "")
+    assert text.splitlines()[-1].startswith("DIFFERENT")
+    _, bad = run(table_kernel(0x300, other_lit="00000020"))                 # a literal that does not follow the s_getpc_b64 pair counts
+    assert bad
+    text, bad = run(table_kernel(0x300), dict(meta, **{".vgpr_count": "9"}))                                  # metadata alone
+    assert bad and "    meta  _Z1tv:" in text
+    text, bad = mod.compare(parent, {"tower_kernels.o": (listing(0x0), {"_Z1kv": meta, "_Z2k2v": meta})})     # a kernel that vanished
+    assert bad and "kernels.o: code  _Z1tv: in the first build only" in text
+    twice = dict(parent, **{"other.o": (table_kernel(0x0, mul="v_mul_f32_e32 v7, s6, v3", mul_enc="0A0E0606"), {"_Z1tv": meta})})
+    text, bad = mod.compare(parent, twice)                                  # one symbol in two units: only one body can be compared
+    assert bad and "second build: other.o: code  _Z1tv: defined in kernels.o too, only that one is compared" in text
