@@ -1,7 +1,8 @@
 // attention_mfma.hip -- MFMA attention for the two 16-bit engines (bf16 / f16).  Short CLIP sequences (S <= 128: 50 vision tokens, 77 text tokens)
 // take the single-pass kernel: one workgroup per (image|caption, head), one wavefront per block of 32 queries,
 // v_mfma_f32_32x32x16_bf16 / _f16 for both products.  Longer ones (ViT-B/16, ViT-L/14[@336]) take the chunked
-// online-softmax kernel further down, built from the same pieces.
+// online-softmax kernel further down.  Both, and the fused text kernel of qkv_attention.hip, take the LDS images, the fragment
+// reads, the mask, the P V step and the output staging from attention_mfma_dev.h, where they are written once.
 //
 //   scores^T = K Q^T   (operands swapped): a lane owns ONE query column (lane&31) and
 //                      16 keys per 32-key tile, so the softmax row reductions are a
@@ -15,32 +16,13 @@
 //                      ds_read_b64_tr_b16 (two [keys][32] images with 64-byte rows -> conflict-free).
 //   Softmax statistics, the running sum and the 1/l normalisation are fp32
 //   (modeling_clip.py:271); P is rounded to the operand type only as the MFMA operand.
+#include "attention_mfma_dev.h"
 #include "dispatch.h"
 #include "kernels.h"
 
 namespace plipmi {
 
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-typedef __attribute__((ext_vector_type(4))) short i16x4;
-
-// V stays row-major in LDS (whole 16-byte pieces straight from the global rows) as two [keys][32 columns] images,
-// one per 32-wide head-dim tile, 64-byte rows.  ds_read_b64_tr_b16 then hands lane (d = lane&31, g = lane>>5) the
-// four keys k0+4g .. k0+4g+3 of column d -- exactly one half of the V^T MFMA fragment under the key permutation
-// described above -- with every 32-lane half of the instruction touching each of the 64 banks once (4 rows x 64 B).
-// Per-lane byte offset inside an image; the (tile, sub-block, image) terms are compile-time immediates.
-__device__ __forceinline__ int vtr_lane_offset(int lrow, int hi) {
-  return (((lrow & 15) >> 2) + 4 * hi) * 64 + ((lrow & 3) * 4 + (lrow >> 4) * 16) * 2;
-}
-template <typename H>
-__device__ __forceinline__ typename half_traits<H>::x8 vtr_fragment(const char* vs, int byte_off) {
-  typedef __attribute__((address_space(3))) i16x4* lds_ptr;
-  const i16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(vs + byte_off));
-  const i16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(vs + byte_off + 8 * 64));  // keys +8
-  typedef __attribute__((ext_vector_type(8))) short i16x8;
-  const i16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(typename half_traits<H>::x8, v);
-}
+using namespace attn_dev;
 
 // One (sample, head) problem per workgroup.  (Two problems per workgroup with a register prefetch of the next K / V rows
 // was measured slower in round 2 -- registers: three waves per SIMD instead of six to eight -- and is gone.)
@@ -53,7 +35,6 @@ __global__ __launch_bounds__(64 * KT) __attribute__((amdgpu_waves_per_eu(4, 4)))
                                                                  const int* __restrict__ cu /* packed rows: sample b owns rows
                                                                  cu[b] .. cu[b+1]-1 of qkv / out (nullptr: b*S .. b*S+S-1) */) {
   using X8 = typename half_traits<HT>::x8;
-  using X4 = typename half_traits<HT>::x4;
   constexpr int SP = 32 * KT;   // padded sequence
   constexpr int NT = 64 * KT;
   constexpr int NP = SP * 8 / NT;   // 16-byte pieces of K (and of V) per thread: 4
@@ -61,10 +42,7 @@ __global__ __launch_bounds__(64 * KT) __attribute__((amdgpu_waves_per_eu(4, 4)))
   // fragment-shaped (16 B from each of 32 rows per instruction, which costs the texture-address unit 2x the
   // time for the same bytes); the LDS image uses the GEMM's XOR swizzle so the fragment ds_read_b128 are
   // conflict-free.  V keeps its row-major form (two [SP][32] images) and is transposed by the LDS read itself.
-  // The second V image starts 64 bytes past a 128-byte boundary: the eight 16-byte pieces of one V row (four per image)
-  // then cover all 32 write banks once instead of hitting the same 16 twice (SQ_LDS_BANK_CONFLICT, round 1: half of
-  // the 3.9e5 conflict cycles per launch; the other half was the output staging below).
-  constexpr int VIMG = SP * 64 + 64;
+  constexpr int VIMG = SP * 64 + 64;   // v_image: the second image 64 bytes past a 128-byte boundary
   __shared__ __attribute__((aligned(16))) char Ks[SP * 128];
   __shared__ __attribute__((aligned(16))) char Vs[2 * VIMG];
   __shared__ unsigned long long mk[4];
@@ -106,8 +84,8 @@ __global__ __launch_bounds__(64 * KT) __attribute__((amdgpu_waves_per_eu(4, 4)))
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int e = tid + i * NT, row = e >> 3, c = e & 7;
-      *reinterpret_cast<u32x4*>(Ks + row * 128 + ((c ^ ((row >> 1) & 7)) << 4)) = kreg[i];
-      *reinterpret_cast<u32x4*>(Vs + (c >> 2) * VIMG + row * 64 + (c & 3) * 16) = vreg[i];
+      *reinterpret_cast<u32x4*>(k_image(Ks, row, c)) = kreg[i];
+      *reinterpret_cast<u32x4*>(v_image(Vs, row, c, VIMG)) = vreg[i];
     }
     // Q fragments (B operand) straight from global memory: Q[query = lrow][d = 16ks + 8hi .. +7].  Only this wave reads
     // these rows, so an LDS image of Q would only cost residency (8-16 KB per workgroup = a third of its LDS).
@@ -136,47 +114,32 @@ __global__ __launch_bounds__(64 * KT) __attribute__((amdgpu_waves_per_eu(4, 4)))
       for (int r = 0; r < 16; ++r) sc[t][r] = 0.f;
       if (live) {
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          const u32x4 kf = *reinterpret_cast<const u32x4*>(Ks + (32 * t + lrow) * 128 + (((ks * 2 + hi) ^ lsw) << 4));
-          sc[t] = half_traits<HT>::mfma32(__builtin_bit_cast(X8, kf), __builtin_bit_cast(X8, qf[ks]), sc[t]);
-        }
+        for (int ks = 0; ks < 4; ++ks) mma16<HT>(sc[t], image_fragment(Ks, 32 * t + lrow, ks, hi, lsw), qf[ks]);
       }
-      // The keys this lane may use in the tile, as ONE 32-bit word: validity (padding / attention_mask) AND, under the causal
-      // mask, keys 32t + j <= query  <=>  j <= d = query - 32t.  Slot r of the accumulator holds key 32t + 4hi + (r&3) + 8(r>>2):
-      // after a shift by 4hi its bit sits at a compile-time position, so masking a score is a 1-bit field extract (0 / -1),
-      // an AND that turns it into 0.0 / -inf, and an add -- no compares, no 64-bit shifts, no branches.  (The two-operation form,
-      // a bit select against -inf, was miscompiled by this hipcc: its v_bitop3_b32 folding mixed the elements' masks.)
       // (round 6) a tile every query of the wave may use entirely -- all 32 keys valid and, under the causal mask, wholly below the
       // diagonal: nothing to mask (wave-uniform test; the 50-token vision tower's first key tile is always one)
       if (live && vw[t] == 0xffffffffu && (!causal || 32 * t + 31 <= q0)) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) rmax = fmaxf(rmax, sc[t][r]);
+        max_scores(sc[t], rmax);
         continue;
       }
-      unsigned bits = live ? vw[t] : 0u;
+      unsigned bits = live ? vw[t] : 0u;   // the keys this lane may use in the tile: validity AND causal limit
       if (causal) {
-        const int d = qidx - 32 * t;
+        const int d = qidx - 32 * t;       // causal_bits(d), written out: the call changes this kernel's instructions
         bits &= d < 0 ? 0u : (d >= 31 ? 0xffffffffu : (2u << d) - 1u);
       }
-      const unsigned nbits = ~(bits >> (4 * hi));        // 1 = masked
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const unsigned m = (unsigned)__builtin_amdgcn_sbfe((int)nbits, (r & 3) + 8 * (r >> 2), 1);   // masked ? 0xffffffff : 0
-        sc[t][r] += __builtin_bit_cast(float, m & 0xff800000u);                                       // + (-inf) or + 0
-        rmax = fmaxf(rmax, sc[t][r]);
-      }
+      mask_scores(sc[t], bits, hi, rmax);
     }
     __syncthreads();  // every wave has its scores: the K rows may now be reused as output staging
     if (active) {
       rmax = fmaxf(rmax, __shfl_xor(rmax, 32, 64));
       const float m_use = (rmax == -INFINITY) ? 0.f : rmax;
-      const float m2 = m_use * 1.4426950408889634f;       // exp(x - m) = 2^(x log2 e - m log2 e): one FMA + v_exp_f32 per score
+      const float m2 = m_use * kLog2e;
       float rsum = 0.f;
 #pragma unroll
       for (int t = 0; t < KT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          sc[t][r] = __builtin_amdgcn_exp2f(fmaf(sc[t][r], 1.4426950408889634f, -m2));
+          sc[t][r] = __builtin_amdgcn_exp2f(fmaf(sc[t][r], kLog2e, -m2));
           rsum += sc[t][r];
         }
       rsum += __shfl_xor(rsum, 32, 64);
@@ -193,45 +156,30 @@ __global__ __launch_bounds__(64 * KT) __attribute__((amdgpu_waves_per_eu(4, 4)))
         if (causal && 32 * t > q0 + 31) continue;
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-          X8 pf;
+          const X8 pf = pack_p<HT>(sc[t], s2);
 #pragma unroll
-          for (int jj = 0; jj < 8; ++jj) pf[jj] = (HT)sc[t][8 * s2 + jj];
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) {
-            const X8 vf = vtr_fragment<HT>(vlane, dt * VIMG + (32 * t + 16 * s2) * 64);
-            acc[dt] = half_traits<HT>::mfma32(vf, pf, acc[dt]);
-          }
+          for (int dt = 0; dt < 2; ++dt) acc[dt] = pv_step<HT>(vlane, VIMG, dt, 32 * t + 16 * s2, pf, acc[dt]);
         }
       }
-      // The accumulator layout gives a lane one query ROW (like the GEMM): write the normalised 32 x 64 bf16 tile
-      // into the K rows of its own query range (every wave is past its scores), then store whole 128-byte rows.
-      // Rows 2k and 2k+1 share a swizzle slot; odd rows keep their two 8-byte halves exchanged, so the 16 lanes of a
-      // ds_write_b64 group (16 consecutive rows, same column chunk) touch 16 distinct 8-byte bank pairs.
+      // the normalised 32 x 64 tile into the K rows of the wave's own query range (every wave is past its scores), odd rows
+      // with their halves exchanged, then whole 128-byte rows to memory
       const float inv = 1.0f / rsum;
       char* orow_lds = Ks + (q0 + lrow) * 128;
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          const int d = dt * 32 + 8 * q4 + 4 * hi;                 // 4 consecutive head-dim columns
-          const int c = d >> 3;                                    // 16-byte chunk, half (d&4) inside it
-          const X4 v = {from_f32<HT>(acc[dt][4 * q4 + 0] * inv), from_f32<HT>(acc[dt][4 * q4 + 1] * inv),
-                        from_f32<HT>(acc[dt][4 * q4 + 2] * inv), from_f32<HT>(acc[dt][4 * q4 + 3] * inv)};
-          *reinterpret_cast<X4*>(orow_lds + ((c ^ lsw) << 4) + ((((d >> 2) ^ lrow) & 1) << 3)) = v;
-        }
+        for (int q4 = 0; q4 < 4; ++q4) stage_out4<HT, true>(orow_lds, lrow, hi, lsw, dt, q4, acc[dt], inv);
       __builtin_amdgcn_wave_barrier();
       const int c = lane & 7;
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int r = q0 + it * 8 + (lane >> 3);
-        const u32x4 raw = *reinterpret_cast<const u32x4*>(Ks + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
-        const u32x4 v = (r & 1) ? u32x4{raw[2], raw[3], raw[0], raw[1]} : raw;
+        const u32x4 v = load_out_row<true>(Ks, r, c);
         if (r < Sb) *reinterpret_cast<u32x4*>(out + ((size_t)row0 + r) * D + h * 64 + c * 8) = v;
       }
     }
   }
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // S > 128 (ViT-B/16: 197 tokens, ViT-L/14: 257, ViT-L/14@336: 577): the same two MFMA products, streamed over
@@ -248,10 +196,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                                                               int S, int H, int causal,
                                                               const int64_t* __restrict__ key_mask) {
   using X8 = typename half_traits<HT>::x8;
-  using X4 = typename half_traits<HT>::x4;
   constexpr int SP = 128;
   constexpr int NP = SP * 8 / 256;   // 16-byte pieces of a chunk's K (and V) rows per thread: 4
-  constexpr float kLog2e = 1.4426950408889634f;
   __shared__ __attribute__((aligned(16))) char Qs[SP * 128];
   __shared__ __attribute__((aligned(16))) char Ks[SP * 128];
   __shared__ __attribute__((aligned(16))) char Vs[2 * SP * 64];
@@ -295,7 +241,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int row = (tid + i * 256) >> 3, c = tid & 7;
-      *reinterpret_cast<u32x4*>(Qs + row * 128 + ((c ^ ((row >> 1) & 7)) << 4)) = q16[i];
+      *reinterpret_cast<u32x4*>(k_image(Qs, row, c)) = q16[i];
     }
   }
 
@@ -326,16 +272,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
     for (int i = 0; i < NP; ++i) {   // the chunk fetched during the previous iteration (or the prologue) -> LDS
       const int row = (tid + i * 256) >> 3, c = tid & 7;
-      *reinterpret_cast<u32x4*>(Ks + row * 128 + ((c ^ ((row >> 1) & 7)) << 4)) = kreg[i];
-      *reinterpret_cast<u32x4*>(Vs + (c >> 2) * (SP * 64) + row * 64 + (c & 3) * 16) = vreg[i];
+      *reinterpret_cast<u32x4*>(k_image(Ks, row, c)) = kreg[i];
+      *reinterpret_cast<u32x4*>(v_image(Vs, row, c, SP * 64)) = vreg[i];
     }
     if (ch + 1 < nchunks) fetch(kbase + SP);   // in flight while this chunk is multiplied
     __syncthreads();
     if (!active) continue;
     if (ch == 0) {
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-        qf[ks] = *reinterpret_cast<const u32x4*>(Qs + (q0 + lrow) * 128 + (((ks * 2 + hi) ^ lsw) << 4));
+      for (int ks = 0; ks < 4; ++ks) qf[ks] = image_fragment(Qs, q0 + lrow, ks, hi, lsw);
     }
     // two 64-key halves per staged chunk: 32 score registers live instead of 64 (3 waves/SIMD), one online-softmax
     // update per half
@@ -354,32 +299,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         for (int r = 0; r < 16; ++r) sc[tt][r] = 0.f;
         if (live) {
 #pragma unroll
-          for (int ks = 0; ks < 4; ++ks) {
-            const u32x4 kf = *reinterpret_cast<const u32x4*>(Ks + (32 * t + lrow) * 128 + (((ks * 2 + hi) ^ lsw) << 4));
-            sc[tt] = half_traits<HT>::mfma32(__builtin_bit_cast(X8, kf), __builtin_bit_cast(X8, qf[ks]), sc[tt]);
-          }
+          for (int ks = 0; ks < 4; ++ks) mma16<HT>(sc[tt], image_fragment(Ks, 32 * t + lrow, ks, hi, lsw), qf[ks]);
         }
-        // the keys this lane may use in the tile as ONE 32-bit word (validity AND causal limit), then per score a 1-bit field
-        // extract, an AND that makes it 0.0 / -inf, an add -- the short kernel's form (see there for why not a bit select)
-        unsigned bits = live ? (unsigned)(mhalf[hf] >> (32 * tt)) : 0u;
+        unsigned bits = live ? (unsigned)(mhalf[hf] >> (32 * tt)) : 0u;   // the keys this lane may use: validity AND causal limit
         if (causal) {
-          const int d = qidx - (kbase + 32 * t);
+          const int d = qidx - (kbase + 32 * t);   // causal_bits(d), written out: the call changes this kernel's instructions
           bits &= d < 0 ? 0u : (d >= 31 ? 0xffffffffu : (2u << d) - 1u);
         }
-        if (__ballot(bits != 0xffffffffu) == 0ull) {
-          // every key of the tile is usable by every query of the wave (the common case away from the sequence end and the
-          // diagonal): no masking arithmetic at all
-#pragma unroll
-          for (int r = 0; r < 16; ++r) cmax = fmaxf(cmax, sc[tt][r]);
-        } else {
-          const unsigned nbits = ~(bits >> (4 * hi));        // 1 = masked; slot r holds key 32t + 4hi + (r&3) + 8(r>>2)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const unsigned m = (unsigned)__builtin_amdgcn_sbfe((int)nbits, (r & 3) + 8 * (r >> 2), 1);
-            sc[tt][r] += __builtin_bit_cast(float, m & 0xff800000u);
-            cmax = fmaxf(cmax, sc[tt][r]);
-          }
-        }
+        // every key of the tile usable by every query of the wave (the common case away from the sequence end and the
+        // diagonal): no masking arithmetic at all
+        if (__ballot(bits != 0xffffffffu) == 0ull) max_scores(sc[tt], cmax);
+        else mask_scores(sc[tt], bits, hi, cmax);
       }
       cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
       const float m_new = fmaxf(m_run, cmax);
@@ -411,10 +341,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             pf[jj] = (HT)pv;
           }
 #pragma unroll
-          for (int dt = 0; dt < 2; ++dt) {
-            const X8 vf = vtr_fragment<HT>(vlane, dt * (SP * 64) + (32 * t + 16 * s2) * 64);
-            acc[dt] = half_traits<HT>::mfma32(vf, pf, acc[dt]);
-          }
+          for (int dt = 0; dt < 2; ++dt) acc[dt] = pv_step<HT>(vlane, SP * 64, dt, 32 * t + 16 * s2, pf, acc[dt]);
         }
       }
       l_run = l_run * scale + csum;
@@ -428,20 +355,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const int d = dt * 32 + 8 * q4 + 4 * hi;
-        const int c = d >> 3;
-        const X4 v = {from_f32<HT>(acc[dt][4 * q4 + 0] * inv), from_f32<HT>(acc[dt][4 * q4 + 1] * inv),
-                      from_f32<HT>(acc[dt][4 * q4 + 2] * inv), from_f32<HT>(acc[dt][4 * q4 + 3] * inv)};
-        *reinterpret_cast<X4*>(orow_lds + ((c ^ lsw) << 4) + (d & 4) * 2) = v;
-      }
+      for (int q4 = 0; q4 < 4; ++q4) stage_out4<HT, false>(orow_lds, lrow, hi, lsw, dt, q4, acc[dt], inv);   // this kernel stages without the odd-row exchange
     __builtin_amdgcn_wave_barrier();
     const int c = lane & 7;
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int rl = q0 + it * 8 + (lane >> 3);
       const int r = qbase + rl;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(Qs + rl * 128 + ((c ^ ((rl >> 1) & 7)) << 4));
+      const u32x4 v = load_out_row<false>(Qs, rl, c);
       if (r < S) *reinterpret_cast<u32x4*>(out + ((size_t)b * S + r) * D + h * 64 + c * 8) = v;
     }
   }

@@ -1,5 +1,5 @@
 // gemm_lds.h -- LDS-DMA, write-through store and MFMA helpers of the GEMM kernels (gemm_kernel.h, gemm_skinny.hip,
-// qkv_attention.hip).
+// qkv_attention.hip); attention_mfma_dev.h takes the vector types and mma16 from here.
 #pragma once
 #include "common.h"
 

@@ -120,7 +120,8 @@ hipError_t launch_convert(const float* src, void* dst, int dst_dtype, int rows, 
 hipError_t launch_transpose(const float* src, float* dst, int rows, int cols, hipStream_t s);
 hipError_t launch_scale_copy(const float* src, float* dst, int n, float scale, hipStream_t s);
 
-// ===== attention.hip (the dispatcher and the fp32 VALU kernel), attention_mfma.hip (the MFMA kernels) =====
+// ===== attention.hip (the dispatcher and the fp32 VALU kernel), attention_mfma.hip (the MFMA kernels; their device pieces, shared
+// with qkv_attention.hip, are in attention_mfma_dev.h) =====
 // Multi-head attention over the fused qkv buffer [B*S, 3*D] (q | k | v, head h at columns h*64..), the 1/sqrt(64)
 // scale already folded into q.  out [B*S, D].  causal: key j <= query i.  key_mask: int64 [B,S] or nullptr.
 //   impl 0 = exact fp32 VALU kernel (any dtype), 1 = MFMA kernel (dtype bf16 or f16)

@@ -13,14 +13,15 @@
 //     every gemm.h tile, so q/k/v are the bits the unfused GEMM writes.
 //   * epilogue 1: y = rstd[m] * acc + c2[n] (LayerNorm folded, gemm.h EPI_BIAS_LN), rounded to the operand type, written to
 //     LDS as the Q / K / V images of the four captions (the staging LDS is free by then): Q, K [336][128 B] with the GEMM's
-//     XOR swizzle, V as two row-major [336][64 B] images for ds_read_b64_tr_b16 -- the layouts of attention_mfma.hip.
+//     XOR swizzle, V as two row-major [336][64 B] images for ds_read_b64_tr_b16 -- the layouts of attention_mfma_dev.h.
 //   * epilogue 2: two waves per caption; under the causal mask query block 0 needs one 32-key tile, block 1 two, block 2
-//     three, so one wave takes blocks 0 + 1 and the other block 2 (3 + 3 tile products).  Arithmetic per query block is
-//     attention_mfma_kernel's, instruction for instruction (scores^T = K Q^T, additive -inf masks from one 32-bit word per
-//     tile, exp2 softmax in fp32, O^T = V^T P^T from registers) -- the attention output is BIT-IDENTICAL to the two-kernel
-//     path's (tests/test_gpu_attention.py::test_fused_qkv_attention_matches_the_two_kernels).
+//     three, so one wave takes blocks 0 + 1 and the other block 2 (3 + 3 tile products).  The arithmetic per query block IS
+//     attention_mfma_kernel's -- both call the functions of attention_mfma_dev.h (scores^T = K Q^T, additive -inf masks from one
+//     32-bit word per tile, exp2 softmax in fp32, O^T = V^T P^T from registers) -- so the attention output is BIT-IDENTICAL to
+//     the two-kernel path's (tests/test_gpu_attention.py::test_fused_qkv_attention_matches_the_two_kernels).
 #include <mutex>
 
+#include "attention_mfma_dev.h"
 #include "dispatch.h"
 #include "gemm.h"
 #include "gemm_lds.h"
@@ -38,7 +39,7 @@ constexpr int kNT = 512;
 constexpr int kABytes = kBM * 128, kWBytes = kBN * 128, kStage = kABytes + kWBytes;   // 64 KB per stage
 constexpr int kImgRows = kBM + 16;                      // the last caption's third key tile reads 16 rows past the tile
 constexpr int kQs = 0, kKs = kImgRows * 128, kVs = 2 * kImgRows * 128;
-constexpr int kVImg = kImgRows * 64 + 64;               // second V image 64 B past a 128-B boundary (attention_mfma.hip)
+constexpr int kVImg = kImgRows * 64 + 64;               // second V image 64 B past a 128-B boundary (v_image)
 constexpr int kImgBytes = kVs + 2 * kVImg;
 static_assert(kImgBytes <= 2 * kStage, "the Q / K / V images reuse the staging LDS");
 constexpr int kLnRows = 2 * kStage;                     // rstd of the tile's rows, 320 floats
@@ -60,21 +61,7 @@ struct QkvAttnParams {
   unsigned long long* trace = nullptr;
 };
 
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-typedef __attribute__((ext_vector_type(4))) short i16x4;
-
-__device__ __forceinline__ int vtr_lane_offset(int lrow, int hi) {
-  return (((lrow & 15) >> 2) + 4 * hi) * 64 + ((lrow & 3) * 4 + (lrow >> 4) * 16) * 2;
-}
-template <typename H>
-__device__ __forceinline__ typename half_traits<H>::x8 vtr_fragment(const char* vs, int byte_off) {
-  typedef __attribute__((address_space(3))) i16x4* lds_ptr;
-  const i16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(vs + byte_off));
-  const i16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(vs + byte_off + 8 * 64));  // keys +8
-  typedef __attribute__((ext_vector_type(8))) short i16x8;
-  const i16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(typename half_traits<H>::x8, v);
-}
+using namespace attn_dev;
 
 template <typename T>
 __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(2, 2))) void qkv_attention_kernel(const QkvAttnParams p) {
@@ -249,8 +236,8 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const X4 pk = {from_f32<T>(fmaf(rs[ii], c[0], cb.x)), from_f32<T>(fmaf(rs[ii], c[1], cb.y)),
                        from_f32<T>(fmaf(rs[ii], c[2], cb.z)), from_f32<T>(fmaf(rs[ii], c[3], cb.w))};
         char* dst;
-        if (seg < 2) dst = smem + (seg == 0 ? kQs : kKs) + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4) + half * 8;
-        else dst = smem + kVs + (chunk >> 2) * kVImg + row * 64 + (chunk & 3) * 16 + half * 8;
+        if (seg < 2) dst = k_image(smem + (seg == 0 ? kQs : kKs), row, chunk) + half * 8;
+        else dst = smem + kVs + (chunk >> 2) * kVImg + row * 64 + (chunk & 3) * 16 + half * 8;   // v_image, written out: the call changes instructions
         *reinterpret_cast<X4*>(dst) = pk;
       }
     }
@@ -284,7 +271,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   constexpr int KTL = 3;                                  // 32-key tiles (65 .. 80 tokens: three query blocks, three key tiles)
   // NB query blocks of 32, starting at block `first`, worked through TOGETHER: their MFMA chains and softmax passes are
   // independent, and with two waves per SIMD that interleaving is what covers the LDS and MFMA latencies.  Per block the
-  // arithmetic is attention_mfma_kernel's, operation for operation.
+  // arithmetic is attention_mfma_kernel's: the same functions in the same order.
   auto attend = [&](auto nb_c, int first) __attribute__((always_inline)) {
     constexpr int NB = decltype(nb_c)::value;
     u32x4 qf[NB][4];
@@ -294,8 +281,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int b = 0; b < NB; ++b) {
       const int qidx = 32 * (first + b) + lrow;
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-        qf[b][ks] = *reinterpret_cast<const u32x4*>(Qs + qidx * 128 + (((ks * 2 + hi) ^ lsw) << 4));
+      for (int ks = 0; ks < 4; ++ks) qf[b][ks] = image_fragment(Qs, qidx, ks, hi, lsw);
       rmax[b] = -INFINITY;
     }
 #pragma unroll
@@ -308,10 +294,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int r = 0; r < 16; ++r) sc[b][t][r] = 0.f;
         if (live) {
 #pragma unroll
-          for (int ks = 0; ks < 4; ++ks) {
-            const u32x4 kf = *reinterpret_cast<const u32x4*>(Ks + (32 * t + lrow) * 128 + (((ks * 2 + hi) ^ lsw) << 4));
-            sc[b][t] = half_traits<T>::mfma32(__builtin_bit_cast(X8, kf), __builtin_bit_cast(X8, qf[b][ks]), sc[b][t]);
-          }
+          for (int ks = 0; ks < 4; ++ks) mma16<T>(sc[b][t], image_fragment(Ks, 32 * t + lrow, ks, hi, lsw), qf[b][ks]);
         }
       }
 #pragma unroll
@@ -326,26 +309,16 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (!live) continue;                                 // wave-uniform
         // a tile every query of the block may use entirely (below the diagonal, all 32 keys valid): nothing to mask (wave-uniform)
         if (vw[t] == 0xffffffffu && (!p.causal || 32 * t + 31 <= q0)) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) rmax[b] = fmaxf(rmax[b], sc[b][t][r]);
+          max_scores(sc[b][t], rmax[b]);
           continue;
         }
         unsigned bits = vw[t];
-        if (p.causal) {
-          const int d = qidx - 32 * t;
-          bits &= d < 0 ? 0u : (d >= 31 ? 0xffffffffu : (2u << d) - 1u);
-        }
-        const unsigned nbits = ~(bits >> (4 * hi));        // 1 = masked
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const unsigned m = (unsigned)__builtin_amdgcn_sbfe((int)nbits, (r & 3) + 8 * (r >> 2), 1);   // masked ? 0xffffffff : 0
-          sc[b][t][r] += __builtin_bit_cast(float, m & 0xff800000u);                                    // + (-inf) or + 0
-          rmax[b] = fmaxf(rmax[b], sc[b][t][r]);
-        }
+        if (p.causal) bits &= causal_bits(qidx - 32 * t);
+        mask_scores(sc[b][t], bits, hi, rmax[b]);
       }
       rmax[b] = fmaxf(rmax[b], __shfl_xor(rmax[b], 32, 64));
       const float m_use = (rmax[b] == -INFINITY) ? 0.f : rmax[b];
-      m2[b] = m_use * 1.4426950408889634f;
+      m2[b] = m_use * kLog2e;
       rsum[b] = 0.f;
 #pragma unroll
       for (int t = 0; t < KTL; ++t) {
@@ -357,7 +330,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          sc[b][t][r] = __builtin_amdgcn_exp2f(fmaf(sc[b][t][r], 1.4426950408889634f, -m2[b]));
+          sc[b][t][r] = __builtin_amdgcn_exp2f(fmaf(sc[b][t][r], kLog2e, -m2[b]));
           rsum[b] += sc[b][t][r];
         }
       }
@@ -378,18 +351,12 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
           if (p.causal && 32 * t > 32 * (first + b) + 31) continue;
-          X8 pf;
+          const X8 pf = pack_p<T>(sc[b][t], s2);
 #pragma unroll
-          for (int jj = 0; jj < 8; ++jj) pf[jj] = (T)sc[b][t][8 * s2 + jj];
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) {
-            const X8 vf = vtr_fragment<T>(vlane, dt * kVImg + (32 * t + 16 * s2) * 64);
-            oacc[b][dt] = half_traits<T>::mfma32(vf, pf, oacc[b][dt]);
-          }
+          for (int dt = 0; dt < 2; ++dt) oacc[b][dt] = pv_step<T>(vlane, kVImg, dt, 32 * t + 16 * s2, pf, oacc[b][dt]);
         }
     // normalised 32 x 64 output tiles -> this wave's OWN Q rows (it holds their fragments in registers, nobody else reads
-    // them), then whole 128-byte rows to memory.  Odd rows keep their two 8-byte halves exchanged (bank spread of the
-    // transposing ds_write_b64, attention_mfma.hip).
+    // them), odd rows with their two 8-byte halves exchanged, then whole 128-byte rows to memory.
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
@@ -402,13 +369,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-          for (int q4 = 0; q4 < 4; ++q4) {
-            const int d = dt * 32 + 8 * q4 + 4 * hi;
-            const int c = d >> 3;
-            const X4 v = {from_f32<T>(oacc[b][dt][4 * q4 + 0] * inv), from_f32<T>(oacc[b][dt][4 * q4 + 1] * inv),
-                          from_f32<T>(oacc[b][dt][4 * q4 + 2] * inv), from_f32<T>(oacc[b][dt][4 * q4 + 3] * inv)};
-            *reinterpret_cast<X4*>(orow_lds + ((c ^ lsw) << 4) + ((((d >> 2) ^ lrow) & 1) << 3)) = v;
-          }
+          for (int q4 = 0; q4 < 4; ++q4) stage_out4<T, true>(orow_lds, lrow, hi, lsw, dt, q4, oacc[b][dt], inv);
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -418,8 +379,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int r = 32 * (first + b) + it * 8 + (lane >> 3);
-        const u32x4 raw = *reinterpret_cast<const u32x4*>(Qs + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
-        const u32x4 v = (r & 1) ? u32x4{raw[2], raw[3], raw[0], raw[1]} : raw;
+        const u32x4 v = load_out_row<true>(Qs, r, c);
         if (r < S) *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(p.out) + ((size_t)cap * S + r) * D + head * 64 + c * 8) = v;
       }
   };
