@@ -4,6 +4,11 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import Optional
+
+# torch ships its own libamdhip64; imported FIRST so that libplipmi.so binds to the same HIP runtime instance
+# (two runtimes in one process do not share devices/streams: plipmi_create then sees "no device")
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libplipmi.so")
@@ -39,6 +44,20 @@ class Weights(C.Structure):
         ("t_token_embedding", C.c_void_p), ("t_pos_embedding", C.c_void_p), ("t_final_ln_w", C.c_void_p),
         ("t_final_ln_b", C.c_void_p), ("text_projection", C.c_void_p), ("t_layers", C.POINTER(LayerWeights)),
     ]
+
+
+# which tensor of an HF CLIP state dict each pointer is: the members of Weights, and the members ln1_w .. fc2_b of LayerWeights by
+# their stem (under <tower>.encoder.layers.<i>.<name>.weight / .bias)
+WEIGHT_KEYS = {
+    "v_class_embedding": "vision_model.embeddings.class_embedding", "v_patch_weight": "vision_model.embeddings.patch_embedding.weight",
+    "v_pos_embedding": "vision_model.embeddings.position_embedding.weight", "v_pre_ln_w": "vision_model.pre_layrnorm.weight",
+    "v_pre_ln_b": "vision_model.pre_layrnorm.bias", "v_post_ln_w": "vision_model.post_layernorm.weight",
+    "v_post_ln_b": "vision_model.post_layernorm.bias", "visual_projection": "visual_projection.weight",
+    "t_token_embedding": "text_model.embeddings.token_embedding.weight", "t_pos_embedding": "text_model.embeddings.position_embedding.weight",
+    "t_final_ln_w": "text_model.final_layer_norm.weight", "t_final_ln_b": "text_model.final_layer_norm.bias",
+    "text_projection": "text_projection.weight"}
+LAYER_KEYS = {"ln1": "layer_norm1", "ln2": "layer_norm2", "q": "self_attn.q_proj", "k": "self_attn.k_proj",
+              "v": "self_attn.v_proj", "o": "self_attn.out_proj", "fc1": "mlp.fc1", "fc2": "mlp.fc2"}
 
 
 class KernelStat(C.Structure):
@@ -134,12 +153,6 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
-    try:
-        # torch ships its own libamdhip64; load it FIRST so libplipmi.so binds to the same HIP runtime instance
-        # (two runtimes in one process do not share devices/streams: plipmi_create then sees "no device")
-        import torch  # noqa: F401
-    except ImportError:  # pragma: no cover - the host layer needs torch anyway
-        pass
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(
             f"{LIB_PATH} is missing: the HIP engine is not built. Run `python -m plip_amd.build` "
@@ -173,3 +186,30 @@ def check(rc: int, what: str) -> None:
         raise IndexError(f"{what}: {last_error()}")
     if rc != 0:
         raise PlipmiError(f"{what} failed (code {rc}): {last_error()}")
+
+
+# ---- Python values -> arguments of the entries ----------------------------------------------------------------------------------
+_DTYPES = {"fp32": F32, "f32": F32, "float32": F32, torch.float32: F32,
+           "bf16": BF16, "bfloat16": BF16, torch.bfloat16: BF16,
+           # IEEE half operands: same matrix-core rate as bf16, 8x smaller operand rounding; the reference's own GPU dtype
+           "f16": F16, "fp16": F16, "float16": F16, "half": F16, torch.float16: F16}
+_TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
+
+
+def _code(dt) -> int:
+    return _DTYPES[dt]
+
+
+def _tower_code(tower: str) -> int:
+    if tower not in ("vision", "text"):
+        raise ValueError(f"tower must be 'vision' or 'text', got {tower!r}")
+    return VISION if tower == "vision" else TEXT
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream_ptr(device):
+    """the hipStream_t argument of an entry: the caller's current stream on ``device``"""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)

@@ -6,14 +6,13 @@ GPU tests can compare them with fp64 references, plus the host mirrors of the sp
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional
 
 import torch
 
 from . import _lib
-from .engine import _TORCH_DTYPE, _code, _ptr
+from ._lib import _TORCH_DTYPE, _code, _ptr, _stream_ptr
 
 
 def gemm_nt(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = 0,
@@ -30,7 +29,7 @@ def gemm_nt(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = Non
     with torch.cuda.device(a.device):
         _lib.check(lib.plipmi_gemm_nt_traced(code, epilogue, variant, M, N, K, _ptr(a), _ptr(w), _ptr(bias), float(alpha),
                                              _ptr(out), _ptr(trace),
-                                             C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)),
+                                             _stream_ptr(a.device)),
                    "plipmi_gemm_nt")
     return out
 
@@ -47,7 +46,7 @@ def gemm_nt_ld(a: torch.Tensor, w: torch.Tensor, K: int, bias: Optional[torch.Te
     with torch.cuda.device(a.device):
         _lib.check(lib.plipmi_gemm_nt_ld(code, epilogue, variant, M, N, K, _ptr(a), a.shape[1], _ptr(w), w.shape[1],
                                          _ptr(bias), float(alpha), _ptr(out),
-                                         C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)), "plipmi_gemm_nt_ld")
+                                         _stream_ptr(a.device)), "plipmi_gemm_nt_ld")
     return out
 
 
@@ -60,7 +59,7 @@ def attention(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool = False, k
     out = torch.empty((B * S, H * 64), dtype=qkv.dtype, device=qkv.device)
     with torch.cuda.device(qkv.device):
         _lib.check(lib.plipmi_attention(code, impl, _ptr(qkv), _ptr(out), B, S, H, int(causal), _ptr(key_mask),
-                                        C.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)), "plipmi_attention")
+                                        _stream_ptr(qkv.device)), "plipmi_attention")
     return out
 
 
@@ -77,7 +76,7 @@ def qkv_attention(a: torch.Tensor, w: torch.Tensor, c2: torch.Tensor, stats: tor
     with torch.cuda.device(a.device):
         _lib.check(lib.plipmi_qkv_attention(_code(a.dtype), _ptr(a), _ptr(w), _ptr(c2), _ptr(stats), H, float(eps), _ptr(out),
                                             B, S, H, int(causal), _ptr(key_mask), _ptr(trace),
-                                            C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)), "plipmi_qkv_attention")
+                                            _stream_ptr(a.device)), "plipmi_qkv_attention")
     return out
 
 
@@ -92,7 +91,7 @@ def gemm_nt_ln(mode: int, a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, 
     code, hdt = _code(a.dtype), a.dtype
     M, K = a.shape
     N = w.shape[0]
-    stream = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
+    stream = _stream_ptr(a.device)
     with torch.cuda.device(a.device):
         if mode in (0, 1):
             if out is None:
@@ -186,7 +185,7 @@ def recode_planes(hi: torch.Tensor, lo: torch.Tensor, to_dtype) -> tuple:
     assert hi.is_cuda and lo.is_cuda and hi.is_contiguous() and lo.is_contiguous() and lo.dtype == torch.uint8 and lo.numel() == lo_plane_bytes(M, N)
     with torch.cuda.device(hi.device):
         _lib.check(lib.plipmi_recode_planes(_ptr(hi), _ptr(lo), M, N, frm, to,
-                                            C.c_void_p(torch.cuda.current_stream(hi.device).cuda_stream)), "plipmi_recode_planes")
+                                            _stream_ptr(hi.device)), "plipmi_recode_planes")
     return hi.view(_TORCH_DTYPE[to]), lo
 
 
@@ -215,7 +214,7 @@ def resample_pos(table: torch.Tensor, gh: int, gw: int) -> torch.Tensor:
     out = torch.empty((1 + gh * gw, table.shape[1]), dtype=torch.float32, device=table.device)
     with torch.cuda.device(table.device):
         _lib.check(lib.plipmi_resample_pos(_ptr(table), _ptr(out), n0, int(gh), int(gw), table.shape[1],
-                                           C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)), "plipmi_resample_pos")
+                                           _stream_ptr(table.device)), "plipmi_resample_pos")
     return out
 
 
@@ -232,16 +231,12 @@ def probe_loss_grad(engine, x: torch.Tensor, y: torch.Tensor, wb: torch.Tensor, 
     grad = torch.empty((K, D + 1), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(lib.plipmi_probe_loss_grad(engine._h, _ptr(x), N, D, _ptr(y), K, _ptr(pos_w), _ptr(neg_w), float(alpha), _ptr(wb),
-                                              _ptr(loss), _ptr(grad), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
+                                              _ptr(loss), _ptr(grad), _stream_ptr(x.device)),
                    "plipmi_probe_loss_grad")
     return loss, grad
 
 
 # ---- the kernels around the GEMMs (include/plipmi_test.h, tests/test_gpu_small_kernels.py) ---------------------------------------------
-def _stream(t: torch.Tensor):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _f32(*ts):
     for t in ts:
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
@@ -254,7 +249,7 @@ def attention_probs(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool = Fa
     assert key_mask is None or (key_mask.is_cuda and key_mask.dtype == torch.int64 and key_mask.is_contiguous() and key_mask.shape == (B, S))
     probs = torch.empty((B, H, S, S) if S <= 1024 else (1,), dtype=torch.float32, device=qkv.device)   # S > 1024 is refused before any launch
     with torch.cuda.device(qkv.device):
-        _lib.check(lib.plipmi_attention_probs(_code(qkv.dtype), _ptr(qkv), _ptr(probs), B, S, H, int(causal), _ptr(key_mask), _stream(qkv)),
+        _lib.check(lib.plipmi_attention_probs(_code(qkv.dtype), _ptr(qkv), _ptr(probs), B, S, H, int(causal), _ptr(key_mask), _stream_ptr(qkv.device)),
                    "plipmi_attention_probs")
     return probs
 
@@ -269,7 +264,7 @@ def attention_pooled_rows(qkv: torch.Tensor, rows: torch.Tensor, B: int, S: int,
     out = torch.empty((B, H, S) if S <= 1024 else (1,), dtype=torch.float32, device=qkv.device)
     with torch.cuda.device(qkv.device):
         _lib.check(lib.plipmi_attention_pooled_rows(_code(qkv.dtype), _ptr(qkv), _ptr(rows), _ptr(out), B, S, H, int(causal), _ptr(key_mask),
-                                                    _stream(qkv)), "plipmi_attention_pooled_rows")
+                                                    _stream_ptr(qkv.device)), "plipmi_attention_pooled_rows")
     return out
 
 
@@ -283,7 +278,7 @@ def attention_rollout_step(qkv: torch.Tensor, R_in: Optional[torch.Tensor], B: i
     out = torch.empty((B, S, S) if S <= 1024 else (1,), dtype=torch.float32, device=qkv.device)
     with torch.cuda.device(qkv.device):
         _lib.check(lib.plipmi_attention_rollout_step(_code(qkv.dtype), _ptr(qkv), _ptr(R_in), _ptr(out), B, S, H, int(causal),
-                                                     _ptr(key_mask), _stream(qkv)), "plipmi_attention_rollout_step")
+                                                     _ptr(key_mask), _stream_ptr(qkv.device)), "plipmi_attention_rollout_step")
     return out
 
 
@@ -302,7 +297,7 @@ def layernorm(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: float = 1e
     else:
         y = torch.empty((rows, D), dtype=out_dtype, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(lib.plipmi_layernorm(_ptr(x), xs, _ptr(g), _ptr(b), _ptr(y), _code(out_dtype), rows, D, float(eps), _stream(x)),
+        _lib.check(lib.plipmi_layernorm(_ptr(x), xs, _ptr(g), _ptr(b), _ptr(y), _code(out_dtype), rows, D, float(eps), _stream_ptr(x.device)),
                    "plipmi_layernorm")
     return y
 
@@ -318,7 +313,7 @@ def layernorm_emit(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, dtype, eps
     st = torch.empty((rows, max(D // 64, 1), 2), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(lib.plipmi_layernorm_emit(_code(dtype), _ptr(x), _ptr(g), _ptr(b), _ptr(hi), _ptr(lo), _ptr(st), rows, D, float(eps),
-                                             _stream(x)), "plipmi_layernorm_emit")
+                                             _stream_ptr(x.device)), "plipmi_layernorm_emit")
     return hi, lo, st
 
 
@@ -331,7 +326,7 @@ def fold_ln(w: torch.Tensor, bias: torch.Tensor, g: torch.Tensor, b: torch.Tenso
     wf = torch.empty((rows, K), dtype=dtype, device=w.device)
     c2 = torch.empty((rows,), dtype=torch.float32, device=w.device)
     with torch.cuda.device(w.device):
-        _lib.check(lib.plipmi_fold_ln(_code(dtype), _ptr(w), _ptr(bias), _ptr(g), _ptr(b), _ptr(wf), _ptr(c2), rows, K, float(pre), _stream(w)),
+        _lib.check(lib.plipmi_fold_ln(_code(dtype), _ptr(w), _ptr(bias), _ptr(g), _ptr(b), _ptr(wf), _ptr(c2), rows, K, float(pre), _stream_ptr(w.device)),
                    "plipmi_fold_ln")
     return wf, c2
 
@@ -358,7 +353,7 @@ def text_embed_emit(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, dty
     bad = torch.zeros((1,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.plipmi_text_embed_emit(_code(dtype), int(packed), _ptr(ids), _ptr(tok), _ptr(pos), _ptr(hi), _ptr(lo), _ptr(st), B, S, D,
-                                              vocab, int(eos_id), _ptr(cu), _ptr(rowmap), _ptr(m), _ptr(bad), _stream(ids)),
+                                              vocab, int(eos_id), _ptr(cu), _ptr(rowmap), _ptr(m), _ptr(bad), _stream_ptr(ids.device)),
                    "plipmi_text_embed_emit")
     assert int(bad.item()) == 0, "token id outside the vocabulary"
     return (hi, lo, st, cu, rowmap, m) if packed else (hi, lo, st)
@@ -381,7 +376,7 @@ def pool_rows(x: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, ids: Opti
     out = torch.empty((B, P if wt is not None else D), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(lib.plipmi_pool_rows(0 if wt is not None else 1, _ptr(x), B, S, D, _ptr(ids), int(eos_id), _ptr(ln_w), _ptr(ln_b), float(eps),
-                                        _ptr(wt), P, int(normalize), _ptr(out), _stream(x)), "plipmi_pool_rows")
+                                        _ptr(wt), P, int(normalize), _ptr(out), _stream_ptr(x.device)), "plipmi_pool_rows")
     return out
 
 
@@ -404,7 +399,7 @@ def pool_gather(att: torch.Tensor, hi: torch.Tensor, lo: torch.Tensor, B: int, S
     xp = torch.empty((B, D), dtype=torch.float32, device=att.device)
     with torch.cuda.device(att.device):
         _lib.check(lib.plipmi_pool_gather(_code(att.dtype), _ptr(att), _ptr(hi), _ptr(lo), B, S, D, _ptr(ids), int(eos_id), _ptr(cu), _ptr(attp),
-                                          _ptr(xp), _stream(att)), "plipmi_pool_gather")
+                                          _ptr(xp), _stream_ptr(att.device)), "plipmi_pool_gather")
     return attp, xp
 
 
@@ -417,7 +412,7 @@ def head_gemm(a: torch.Tensor, w: torch.Tensor, scale: float = 1.0) -> torch.Ten
     assert w.shape[1] == K
     out = torch.empty((M, N), dtype=torch.float32, device=a.device)
     with torch.cuda.device(a.device):
-        _lib.check(lib.plipmi_head_gemm(_ptr(a), _ptr(w), _ptr(out), M, N, K, float(scale), _stream(a)), "plipmi_head_gemm")
+        _lib.check(lib.plipmi_head_gemm(_ptr(a), _ptr(w), _ptr(out), M, N, K, float(scale), _stream_ptr(a.device)), "plipmi_head_gemm")
     return out
 
 
@@ -436,7 +431,7 @@ def resize_ragged_tables(in_size: int, out_size: int, first: int = 0, count: Opt
     coef = torch.zeros((count, int(ksize)), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.plipmi_resize_ragged_tables(int(in_size), int(out_size), int(first), count, int(ksize), _ptr(bounds), _ptr(coef),
-                                                   _stream(bounds)), "plipmi_resize_ragged_tables")
+                                                   _stream_ptr(bounds.device)), "plipmi_resize_ragged_tables")
     return bounds, coef
 
 
@@ -458,7 +453,7 @@ def unfold_patches(src: torch.Tensor, out: torch.Tensor, patch: int, kpad: int) 
     B, H, W = (src.shape[0], src.shape[1], src.shape[2]) if u8 else (src.shape[0], src.shape[2], src.shape[3])
     assert src.shape[3 if u8 else 1] == 3 and out.shape[1] == kpad and out.shape[0] >= B * (H // patch) * (W // patch)
     with torch.cuda.device(src.device):
-        _lib.check(lib.plipmi_unfold_patches(_code(out.dtype), int(u8), _ptr(src), _ptr(out), B, H, W, int(patch), int(kpad), _stream(src)),
+        _lib.check(lib.plipmi_unfold_patches(_code(out.dtype), int(u8), _ptr(src), _ptr(out), B, H, W, int(patch), int(kpad), _stream_ptr(src.device)),
                    "plipmi_unfold_patches")
     return out
 
@@ -470,7 +465,7 @@ def cls_rows(cls: torch.Tensor, pos: torch.Tensor, x: torch.Tensor, B: int, toke
     D = cls.numel()
     assert pos.shape[-1] == D and x.dim() == 2 and x.shape[1] == D and x.shape[0] >= B * tokens
     with torch.cuda.device(x.device):
-        _lib.check(lib.plipmi_cls_rows(_ptr(cls), _ptr(pos), _ptr(x), int(B), int(tokens), D, _stream(x)), "plipmi_cls_rows")
+        _lib.check(lib.plipmi_cls_rows(_ptr(cls), _ptr(pos), _ptr(x), int(B), int(tokens), D, _stream_ptr(x.device)), "plipmi_cls_rows")
     return x
 
 
@@ -485,7 +480,7 @@ def gemm_patch(a: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, out: torch.T
     assert np_ >= 1 and M % np_ == 0 and pos.shape[1] == N and out.shape[1] == N and out.shape[0] >= M // np_ * (np_ + 1)
     with torch.cuda.device(a.device):
         _lib.check(lib.plipmi_gemm_patch(_code(a.dtype), int(variant), M, N, K, _ptr(a), a.shape[1], _ptr(w), w.shape[1], _ptr(pos), np_,
-                                         _ptr(out), _stream(a)), "plipmi_gemm_patch")
+                                         _ptr(out), _stream_ptr(a.device)), "plipmi_gemm_patch")
     return out
 
 
@@ -502,7 +497,7 @@ def gemm_patch_gather(src: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, out
     assert out.shape[1] == N and pos.shape[1] == N and out.shape[0] >= B * pos.shape[0]
     with torch.cuda.device(src.device):
         _lib.check(lib.plipmi_gemm_patch_gather(_code(w.dtype), None if u8 else _ptr(src), _ptr(src) if u8 else None, _ptr(w), _ptr(pos),
-                                                _ptr(out), B, H, W, int(patch), N, _stream(src)), "plipmi_gemm_patch_gather")
+                                                _ptr(out), B, H, W, int(patch), N, _stream_ptr(src.device)), "plipmi_gemm_patch_gather")
     return out
 
 
@@ -527,11 +522,11 @@ def gemm_nt_ln_rows(mode: int, a: torch.Tensor, w: torch.Tensor, bias: torch.Ten
         args = (None, 0, float(eps), _ptr(lo), _ptr(hi), _ptr(st))
     with torch.cuda.device(a.device):
         if m_dev is None:
-            _lib.check(lib.plipmi_gemm_nt_ln(_code(a.dtype), mode, int(variant), M, N, K, _ptr(a), _ptr(w), _ptr(bias), *args, _stream(a)),
+            _lib.check(lib.plipmi_gemm_nt_ln(_code(a.dtype), mode, int(variant), M, N, K, _ptr(a), _ptr(w), _ptr(bias), *args, _stream_ptr(a.device)),
                        "plipmi_gemm_nt_ln")
         else:
             _lib.check(lib.plipmi_gemm_nt_ln_rows(_code(a.dtype), mode, int(variant), M, N, K, _ptr(a), _ptr(w), _ptr(bias), *args, _ptr(m_dev),
-                                                  _stream(a)), "plipmi_gemm_nt_ln_rows")
+                                                  _stream_ptr(a.device)), "plipmi_gemm_nt_ln_rows")
 
 
 def attention_packed(qkv: torch.Tensor, out: torch.Tensor, cu: torch.Tensor, S: int, H: int, causal: bool = False,
@@ -548,5 +543,5 @@ def attention_packed(qkv: torch.Tensor, out: torch.Tensor, cu: torch.Tensor, S: 
     assert key_mask is None or (key_mask.is_cuda and key_mask.dtype == torch.int64 and key_mask.is_contiguous() and key_mask.shape == (B, S))
     with torch.cuda.device(qkv.device):
         _lib.check(lib.plipmi_attention_packed(_code(qkv.dtype), int(impl), _ptr(qkv), _ptr(out), B, int(S), H, int(causal), _ptr(key_mask),
-                                               _ptr(cu), _stream(qkv)), "plipmi_attention_packed")
+                                               _ptr(cu), _stream_ptr(qkv.device)), "plipmi_attention_packed")
     return out

@@ -27,7 +27,7 @@ def test_header_declares_and_lib_binds_the_entries():
         assert m, name
         assert len(m.group(1).split(",")) == 10 == len(_lib.TEST_SYMBOLS[name][1]), name
         assert name not in _lib.SYMBOLS and name not in header
-    assert "plipmi_encode_attention_summary" in open(os.path.join(ROOT, "plip_amd", "engine.py")).read()
+    assert "plipmi_encode_attention_summary" in open(os.path.join(ROOT, "plip_amd", "engine_outputs.py")).read()
     # additive: the version number and the entry it extends are as they were
     assert re.search(r"#define PLIPMI_VERSION 412\b", header)
     assert len(_lib.SYMBOLS["plipmi_encode_tower_outputs"][1]) == 11

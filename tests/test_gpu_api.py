@@ -727,3 +727,71 @@ def test_engine_switches_are_constructor_arguments_not_environment(engines, monk
         assert (got - want).abs().max().item() < 6e-2           # another rounding plan of the same network
     finally:
         same.engine.close(); other.engine.close()
+
+
+def test_a_derived_engine_starts_with_state_of_its_own():
+    """Engine.clone / Engine.at_resolution share the configuration and the packed weights and nothing that is written after
+    construction: every container, tensor, stream, engine and handle an engine holds once all of its lazy caches are filled is
+    that engine's alone (checked over vars(), so a cache added later is covered too), while what the caller set on the
+    instance -- use_lanes, pair_vision_priority, max_resolutions -- is inherited at the moment of the call."""
+    import collections
+    import ctypes as C
+    from plip_amd.engine import Engine
+    from plip_amd.model import PlipModel
+    cfg, sd, px, ids, mask = case_inputs("tiny_b6")
+    n = cfg.image_size
+    rs = np.random.RandomState(17)
+    same = torch.from_numpy(rs.randint(0, 256, (2, 40, 48, 3), dtype=np.uint8))
+    ragged = [rs.randint(0, 256, (40, 48, 3), dtype=np.uint8), rs.randint(0, 256, (50, 36, 3), dtype=np.uint8)]
+    tiles = torch.from_numpy(rs.randint(0, 256, (9, n, n, 3), dtype=np.uint8))
+    eng = PlipModel(cfg, sd, dtype="bf16", max_batch=8).engine
+    twin = None
+    try:
+        with pytest.raises(ValueError):                        # NOT the parent commit's behaviour: a misspelt tower used to run the text tower
+            eng.hidden("vison", 0, torch.from_numpy(px[:1]))
+        eng.pair_vision_priority, eng.max_resolutions = True, 2
+        want_tiles = eng.resize_crop_u8(same)
+        eng.resize_crop_ragged(ragged)
+        eng.encode_pair(torch.from_numpy(px[:2]), torch.from_numpy(ids[:2]), torch.from_numpy(mask[:2]))
+        want = eng.encode_image_u8(tiles)                      # nine rows at max_batch 8: two chunks, the second on a lane
+        r0 = eng.at_resolution(2 * n, n)
+        torch.cuda.synchronize()
+        lane = eng._lanes[0]
+        assert r0.use_lanes is True                            # the parent's value when r0 was made ...
+        eng.use_lanes = False                                  # ... and when r is
+        twin, r = eng.clone(), eng.at_resolution(n, 2 * n)
+
+        kinds = (dict, list, torch.Tensor, torch.cuda.Stream, Engine, C.c_void_p)      # OrderedDict is a dict
+
+        def owned(e):
+            """ids of what ``e`` holds in its attributes and one level into its containers"""
+            got = {}
+            for name, v in vars(e).items():
+                inner = list(v.values()) if isinstance(v, dict) else list(v) if isinstance(v, list) else []
+                for x in [v] + inner:
+                    if isinstance(x, kinds) and x is not eng:
+                        got[id(x)] = name
+            return got
+
+        mine = owned(eng)
+        assert {"_h", "_lanes", "_vis", "_resolutions", "_resize_plans", "_ragged_ws"} <= set(mine.values()), sorted(set(mine.values()))
+        for other in (twin, r, r0, lane):
+            theirs = owned(other)
+            shared = [(mine[i], theirs[i]) for i in mine if i in theirs]
+            assert not shared, shared
+        assert r._res_root is eng and isinstance(eng._resolutions, collections.OrderedDict)
+        assert twin.use_lanes is False and lane.use_lanes is False             # a clone is a lane whatever its source had set
+        assert r.use_lanes is False and r0.use_lanes is True
+        for other in (twin, r):
+            assert other.pair_vision_priority is True and other.max_resolutions == 2
+        assert (r.max_batch, r.image_hw, twin.max_batch, twin.image_hw) == (max(1, 8 * eng.v_tokens // r.v_tokens), (n, 2 * n), 8, (n, n))
+        assert r.at_resolution(2 * n, n) is r0 and r.at_resolution(n, 2 * n) is r
+        assert torch.equal(twin.resize_crop_u8(same), want_tiles) and torch.equal(twin.encode_image_u8(tiles), want)
+        torch.cuda.synchronize()
+        eng.close()
+        assert not r._h.value and not r0._h.value and not lane._h.value and twin._h.value
+        assert torch.equal(twin.encode_image_u8(tiles), want)
+    finally:
+        eng.close()
+        if twin is not None:
+            twin.close()

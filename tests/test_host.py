@@ -53,11 +53,166 @@ def test_product_modules_do_not_call_the_test_header():
             src = open(os.path.join(dirpath, f)).read()
             assert "kernel_entries" not in src, f
             for name in _lib.TEST_SYMBOLS:
-                if name == "plipmi_debug_hidden" and f == "engine.py":
+                if name == "plipmi_debug_hidden" and f == "engine_outputs.py":
                     continue
                 assert name not in src, (f, name)
     for f in ("bench.py", "__graft_entry__.py"):
         assert "kernel_entries" not in open(os.path.join(ROOT, f)).read(), f
+
+
+_T, _OT, _OI = "'torch.Tensor'", "'Optional[torch.Tensor]'", "'Optional[int]'"
+_STREAM, _ENGINE = "\"'torch.cuda.Stream'\"", "\"'Engine'\""
+# Engine's public surface, recorded on the commit before engine.py was split by concern: name -> (kind, signature / value)
+ENGINE_SURFACE = {
+    "at_resolution": ("function", f"(self, height: 'int', width: 'int') -> {_ENGINE}"),
+    "attention_summary": ("function", f"(self, tower: 'str', inp: {_T}, attention_mask: {_OT} = None, pooled_attention: 'bool' = True, "
+                          f"rollout: 'bool' = True, rollout_matrix: 'bool' = False, eos_token_id: {_OI} = None) -> 'AttentionSummary'"),
+    "check_async": ("function", "(self, synchronize: 'bool' = True) -> 'None'"),
+    "clone": ("function", f"(self) -> {_ENGINE}"),
+    "close": ("function", "(self)"),
+    "encode_image": ("function", f"(self, pixels: {_T}, normalize: 'bool' = False) -> {_T}"),
+    "encode_image_u8": ("function", f"(self, tiles: {_T}, normalize: 'bool' = False) -> {_T}"),
+    "encode_pair": ("function", f"(self, pixels: {_T}, input_ids: {_T}, attention_mask: {_OT} = None, normalize: 'bool' = True, overlap: 'bool' = True)"),
+    "encode_text": ("function", f"(self, input_ids: {_T}, attention_mask: {_OT} = None, normalize: 'bool' = False, eos_token_id: {_OI} = None) -> {_T}"),
+    "hidden": ("function", f"(self, tower: 'str', layer: 'int', inp: {_T}) -> {_T}"),
+    "image_hw": ("property", "(self)"),
+    "join_lanes": ("function", "(self, lanes)"),
+    "l2_normalize_": ("function", f"(self, x: {_T}) -> {_T}"),
+    "lane_loop": ("function", "(self)"),
+    "lanes": ("function", "(self, n: 'int' = 2)"),
+    "logit_scale_exp": ("property", "(self) -> 'float'"),
+    "logits": ("function", f"(self, image_embeds: {_T}, text_embeds: {_T}, scale: 'float' = 1.0, want_text: 'bool' = True, want_argmax: 'bool' = False)"),
+    "max_resolutions": ("value", "4"),
+    "pair_stream": ("function", f"(self, main: {_STREAM}) -> {_STREAM}"),
+    "probe_fit": ("function", "(self, x, y, n_classes: 'int', alpha: 'float', class_weight: 'Optional[str]' = 'balanced', max_iter: 'int' = 1000, "
+                  "gtol: 'float' = 2e-08, coef_init=None, intercept_init=None)"),
+    "probe_predict": ("function", f"(self, x, coef, intercept, return_decision: 'bool' = False, chunk_rows: {_OI} = None)"),
+    "profile": ("function", "(self, result: 'list')"),
+    "resize_crop_ragged": ("function", f"(self, images, crop: 'str' = 'torchvision', n_px: {_OI} = None) -> {_T}"),
+    "resize_crop_u8": ("function", f"(self, images_u8: {_T}, crop: 'str' = 'torchvision') -> {_T}"),
+    "set_graph_batch": ("function", "(self, max_batch: 'int')"),
+    "set_latency_batch": ("function", "(self, max_batch: 'int')"),
+    "set_text_packing": ("function", "(self, on: 'bool')"),
+    "similarity_topk": ("function", f"(self, keys: {_T}, space: {_T}, k: 'int', return_values: 'bool' = False)"),
+    "streams_overlap": ("function", f"(self, a: {_STREAM}, b: {_STREAM}) -> 'float'"),
+    "topk": ("function", f"(self, scores: {_T}, k: 'int') -> {_T}"),
+    "tower_outputs": ("function", f"(self, tower: 'str', inp: {_T}, attention_mask: {_OT} = None, output_hidden_states: 'bool' = False, "
+                      f"output_attentions: 'bool' = False, eos_token_id: {_OI} = None) -> 'TowerOutput'"),
+    "tower_shape": ("function", "(self, tower: 'str')"),
+    "use_lanes": ("value", "True"),
+    "v_tokens": ("property", "(self) -> 'int'"),
+}
+# ... and the module-level names tests, tools, plip.py and kernel_entries.py import from plip_amd.engine
+ENGINE_MODULE_SURFACE = {
+    "DEFAULT_TEXT_F16_LAYERS": ("value", "8"),
+    "Engine": ("class", "(cfg: 'PlipConfig', state_dict: 'Mapping[str, object]', device='cuda:0', dtype='bf16', max_batch: 'int' = 256, *, "
+               "ln_fold: 'bool' = True, pooled_last_block: 'bool' = True, pack_captions: 'bool' = False, mfma_attention: 'bool' = True, "
+               f"graph_batch: {_OI} = None, text_f16: 'bool' = False, text_f16_layers: {_OI} = None, latency_batch: 'int' = 0, "
+               f"pass_batch: {_OI} = None, _config_struct_size: {_OI} = None)"),
+    "_TORCH_DTYPE": ("value", "{0: torch.float32, 1: torch.bfloat16, 2: torch.float16}"),
+    "_code": ("function", "(dt) -> 'int'"),
+    "_ptr": ("function", f"(t: {_OT})"),
+    "heads_engine": ("function", f"(device='cuda:0') -> {_ENGINE[1:-1]}"),
+    "ragged_blob": ("function", f"(images, out: {_OT} = None)"),
+    "ragged_blob_bytes": ("function", "(images) -> 'int'"),
+}
+
+
+def _surface_entry(v):
+    import inspect
+    if isinstance(v, property):
+        return ("property", str(inspect.signature(v.fget)))
+    if inspect.isfunction(v) or inspect.isclass(v):
+        return ("class" if inspect.isclass(v) else "function", str(inspect.signature(v)))
+    return ("value", repr(v))
+
+
+def test_engine_surface_did_not_move_when_the_module_was_split():
+    """plip_amd.engine is the import point of the host layer whichever module a method lives in: every public attribute of Engine
+    and every module-level name others import keep their kind, signature and value; the stream tables are the very dicts the
+    stream code uses (tools/exp writes into them); what a derived engine inherits, and that a never-finished engine closes."""
+    import inspect
+    import plip_amd.engine as E
+    import plip_amd.engine_streams as ES
+    got = {k: _surface_entry(inspect.getattr_static(E.Engine, k)) for k in dir(E.Engine) if not k.startswith("_")}
+    assert got == ENGINE_SURFACE, {k: (got.get(k), ENGINE_SURFACE.get(k)) for k in set(got) | set(ENGINE_SURFACE) if got.get(k) != ENGINE_SURFACE.get(k)}
+    got = {k: _surface_entry(getattr(E, k)) for k in ENGINE_MODULE_SURFACE}
+    assert got == ENGINE_MODULE_SURFACE, {k: (got[k], ENGINE_MODULE_SURFACE[k]) for k in got if got[k] != ENGINE_MODULE_SURFACE[k]}
+    assert E._PAIR_STREAMS is ES._PAIR_STREAMS and E._SIDE_STREAMS is ES._SIDE_STREAMS and type(E._PAIR_STREAMS) is type(E._SIDE_STREAMS) is dict
+    assert E.ragged_blob.__module__ == "plip_amd.engine_resize" and E.Engine.hidden.__module__ == "plip_amd.engine_outputs"
+
+    # an engine whose construction raised before it had a handle closes without raising, from close() and from __del__
+    e = object.__new__(E.Engine)
+    with pytest.raises(TypeError):
+        e.__init__()
+    e.__del__()
+    e = object.__new__(E.Engine)
+    with pytest.raises(AttributeError):
+        e.__init__(None, {})
+    e.close()
+    e.__del__()
+
+
+def test_derived_engines_inherit_what_the_caller_set_and_own_their_state(monkeypatch):
+    """Engine.clone / Engine.at_resolution through one helper, on a stand-in library: the shared attributes and whatever the caller
+    set on the instance are inherited at the moment of the call, clone() forces use_lanes off and keeps the size, at_resolution()
+    keeps use_lanes and sets max_batch, pass_batch, the image size and the root; every own attribute is fresh."""
+    import contextlib
+    import ctypes as C
+    import torch
+    import plip_amd.engine as E
+    monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
+
+    class Lib:
+        made, destroyed = [], []
+
+        def plipmi_clone(self, src, out):
+            out._obj.value = 100 + len(self.made)
+            self.made.append(("clone", src.value))
+            return 0
+
+        def plipmi_clone_resolution(self, src, h, w, mb, out):
+            out._obj.value = 100 + len(self.made)
+            self.made.append(("resolution", src.value, h, w, mb))
+            return 0
+
+        def plipmi_get_pass_batch(self, h):
+            return 7
+
+        def plipmi_destroy(self, h):
+            self.destroyed.append(h.value)
+
+    eng = object.__new__(E.Engine)
+    eng._init_own_state()
+    own = set(vars(eng))
+    assert own == {"_h", "_lanes", "_no_lanes", "_vis", "pair_stream_ratio", "_resolutions", "_res_root", "_image_hw", "_resize_plans", "_ragged_ws"}
+    eng._h = C.c_void_p(1)
+    eng.cfg, eng.device, eng.lib, eng.max_batch, eng.pass_batch = get_config("tiny"), torch.device("cuda", 0), Lib(), 8, 0
+    eng.pair_vision_priority, eng.max_resolutions = True, 2
+    eng._resize_plans["k"], eng._ragged_ws, eng._vis, eng._no_lanes, eng.pair_stream_ratio = 1, torch.zeros(1), object(), 1, 1.0
+    n = eng.cfg.image_size
+    r0 = eng.at_resolution(2 * n, n)
+    assert r0.use_lanes is True                                 # the class default, as the parent has it now
+    eng.use_lanes = False
+    twin, r = eng.clone(), eng.at_resolution(n, 2 * n)
+    assert eng.lib.made == [("resolution", 1, 2 * n, n, r0.max_batch), ("clone", 1), ("resolution", 1, n, 2 * n, r.max_batch)]
+    fresh = object.__new__(E.Engine)
+    fresh._init_own_state()
+    for other in (twin, r, r0):
+        assert other.pair_vision_priority is True and other.max_resolutions == 2 and other.cfg is eng.cfg and other.lib is eng.lib
+        for k in own - {"_h", "_image_hw", "_res_root"}:
+            assert vars(other)[k] == vars(fresh)[k] and (vars(other)[k] is None or vars(other)[k] is not vars(eng)[k]), k
+    assert twin.use_lanes is False and r.use_lanes is False and r0.use_lanes is True
+    assert (twin.max_batch, twin.pass_batch, twin.image_hw, twin._res_root) == (8, 0, (n, n), None)
+    assert (r.max_batch, r.pass_batch, r.image_hw, r._res_root) == (max(1, 8 * eng.v_tokens // r.v_tokens), 7, (n, 2 * n), eng)
+    assert r.at_resolution(2 * n, n) is r0 and list(eng._resolutions) == [(n, 2 * n), (2 * n, n)]
+    lane = r.clone()                                            # plipmi_clone keeps the size: so does the host's view of it
+    assert lane.image_hw == (n, 2 * n) and lane.use_lanes is False and lane._h.value == 103
+    r2 = eng.at_resolution(n, 3 * n)                            # a third size: the least recently used (r) is closed
+    assert not r._h.value and r0._h.value and eng.lib.destroyed == [102]
+    eng.close()
+    assert not eng._h.value and not r0._h.value and not r2._h.value and twin._h.value and sorted(eng.lib.destroyed) == [1, 100, 102, 104]
+    twin.close(), lane.close()
 
 
 def test_library_reads_no_environment_variables():

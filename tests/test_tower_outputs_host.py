@@ -71,7 +71,7 @@ def test_header_declares_and_lib_binds_the_entries():
         assert m, name
         assert len(m.group(1).split(",")) == nargs == len(_lib.SYMBOLS[name][1]), name
         assert name not in _lib.TEST_SYMBOLS
-    assert "plipmi_encode_tower_outputs" in open(os.path.join(ROOT, "plip_amd", "engine.py")).read()
+    assert "plipmi_encode_tower_outputs" in open(os.path.join(ROOT, "plip_amd", "engine_outputs.py")).read()
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
