@@ -77,7 +77,10 @@ int plipmi_gemm_nt_traced(int dtype, int epilogue, int variant, int M, int N, in
  *           both planes read and written in place; st_out as in mode 2.  This is the form the engine runs (6 bytes per element
  *           of epilogue traffic; the hi plane is the next GEMM's A operand)
  *   mode 4: mode 3 that READS the planes in dtype's split format and WRITES them in the other 16-bit type's (the last f16
- *           block of a bf16 text tower with plipmi_config.text_f16_layers hands the stream over without a re-coding pass) */
+ *           block of a bf16 text tower with plipmi_config.text_f16_layers hands the stream over without a re-coding pass)
+ * variant as plipmi_gemm_nt; -3 (the small-M split-K kernel, K % 256 == 0) runs modes 0 .. 3 -- mode 3 there adds (x + bias) + A.W^T
+ * as the tiles do, mode 2 x + (A.W^T + bias) -- and refuses mode 4: it writes the planes in the type it reads them in, the engine
+ * re-codes them in a pass of their own on that path. */
 int plipmi_gemm_nt_ln(int dtype, int mode, int variant, int M, int N, int K, const void* A, const void* W, const float* bias,
                       const float* stats, int ns, float eps, void* C, void* xb_out, float* st_out, void* stream);
 
@@ -175,7 +178,8 @@ int plipmi_unfold_patches(int dtype, int from_u8, const void* src, void* out, in
 int plipmi_cls_rows(const float* cls, const float* pos, float* x, int B, int tokens, int D, void* stream);
 /* The patch GEMM (gemm.h EPI_PATCH): C fp32 [B * (np + 1), N], token row img * (np + 1) + 1 + p = A[img * np + p, :K] . W[n, :K] +
  * pos[1 + p, n]; A [M = B * np, lda], W [N, ldw] (dtype), pos fp32 [np + 1, N].  CLS rows are not touched.  variant as plipmi_gemm_nt
- * (-1 the cost model, 0 .. a tile, -2 the naive kernel).  M % np == 0, N % 4 == 0, lda / ldw >= K and multiples of 16 bytes. */
+ * (-1 the cost model, 0 .. a tile, -2 the naive kernel, -3 the small-M split-K kernel: 16-bit types, N % 64 == 0, K % 256 == 0).
+ * M % np == 0, N % 4 == 0, lda / ldw >= K and multiples of 16 bytes. */
 int plipmi_gemm_patch(int dtype, int variant, int M, int N, int K, const void* A, int lda, const void* W, int ldw, const float* pos,
                       int np, void* C, void* stream);
 /* The same rows from the patch GEMM with im2col on load (gemm.h ADDR 2 / 3, the ring tile), at ANY batch: exactly one of pixels (fp32

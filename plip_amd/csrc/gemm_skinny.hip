@@ -172,7 +172,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_kernel(const GemmParams p
     const float xo[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
     float o[8], s = 0.f;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { o[e] = xo[e] + (v[e] + bias[e]); s += o[e]; }   // same association as the big kernel: x + (acc + bias)
+    for (int e = 0; e < 8; ++e) { o[e] = xo[e] + (v[e] + bias[e]); s += o[e]; }   // x + (acc + bias): NOT the split form's (x + bias) + acc above (= the big kernel's); the pooled last block's bits are pinned on this order
     if (in_range) {
       *reinterpret_cast<float4*>(crow) = make_float4(o[0], o[1], o[2], o[3]);
       *reinterpret_cast<float4*>(crow + 4) = make_float4(o[4], o[5], o[6], o[7]);
@@ -212,9 +212,8 @@ int launch_skinny(const GemmParams& p, hipStream_t s) {
     if (nb % 2 == 0) return launch_skinny_nb<T, EPI, 8, 2>(p, s);
     return launch_skinny_nb<T, EPI, 8, 1>(p, s);
   }
-  const int nb = blocks / 4;
+  const int nb = blocks / 4;                         // odd here (K % 256 == 0, blocks % 8 != 0): there is no (4, 2) form
   if (nb % 3 == 0) return launch_skinny_nb<T, EPI, 4, 3>(p, s);
-  if (nb % 2 == 0) return launch_skinny_nb<T, EPI, 4, 2>(p, s);
   return launch_skinny_nb<T, EPI, 4, 1>(p, s);
 }
 

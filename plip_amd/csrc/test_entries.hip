@@ -39,7 +39,8 @@ static int gemm_nt_ln_entry(int dtype, int mode, int variant, int M, int N, int 
   if (mode < 2 && (!stats || ns <= 0)) return fail(PLIPMI_ERR_INVALID, "mode 0/1 need the row statistics");
   if (mode < 2 && ns % 2) return fail(PLIPMI_ERR_INVALID, "mode 0/1 read the statistics two slices at a time: ns = %d must be even (LayerNorm widths are multiples of 128)", ns);
   if (mode >= 2 && (!xb_out || !st_out || N % kLnSlice)) return fail(PLIPMI_ERR_INVALID, "mode 2/3 need xb_out, st_out and N %% 64 == 0");
-  if (mode >= 3 && variant == -3) return fail(PLIPMI_ERR_INVALID, "the small-M kernel has no split-plane epilogue");
+  if (mode == 4 && variant == -3)    // gemm_skinny.hip's EPI_RESID_SPLIT ignores planes_other: it would write dtype's own format
+    return fail(PLIPMI_ERR_INVALID, "mode 4 at variant -3: the small-M kernel writes the planes in the type it reads them in (the engine re-codes them in enter_block instead)");
   GemmParams p = make_params(A, W, C, bias, M, N, K, K, K, N);
   p.m_dev = m_dev;
   p.ln_stats = stats; p.ln_ns = ns; p.ln_inv_d = ns > 0 ? 1.0f / (float)(ns * kLnSlice) : 0.f; p.ln_eps = eps;
@@ -280,10 +281,15 @@ int plipmi_gemm_patch(int dtype, int variant, int M, int N, int K, const void* A
   if (M < 0 || N <= 0 || N % 4 || K <= 0 || !A || !W || !C || !pos || lda < K || ldw < K || lda % per16 || ldw % per16)
     return fail(PLIPMI_ERR_INVALID, "bad shape / null pointer / leading dimension (N %% 4 == 0; lda, ldw >= K and multiples of 16 bytes)");
   if (np <= 0 || M % np) return fail(PLIPMI_ERR_INVALID, "np = %d patches per image must be positive and divide M = %d", np, M);
-  if (variant < -2) return fail(PLIPMI_ERR_INVALID, "variant %d: -1 (cost model), -2 (naive checker) or a tile", variant);
+  if (variant < -3) return fail(PLIPMI_ERR_INVALID, "variant %d: -1 (cost model), -2 (naive checker), -3 (small-M split-K kernel) or a tile", variant);
+  // -3: what gemm_launch_skinny would refuse is refused here, by name, before anything is launched
+  if (variant == -3 && !half_code(dtype)) return fail(PLIPMI_ERR_INVALID, "variant -3: the small-M kernel takes 16-bit operands");
+  if (variant == -3 && (!gemm_skinny_supports(EPI_PATCH, M > 0 ? M : 1, N, K) || lda % 8 || ldw % 8))
+    return fail(PLIPMI_ERR_INVALID, "variant -3: the small-M kernel needs N %% 64 == 0, K %% 256 == 0 and lda, ldw multiples of 8 (got N=%d K=%d lda=%d ldw=%d)", N, K, lda, ldw);
   GemmParams p = make_params(A, W, C, pos, M, N, K, lda, ldw, N);
   p.np = np;
-  const int rc = gemm_launch(dtype, EPI_PATCH, variant, p, reinterpret_cast<hipStream_t>(stream), nullptr);
+  const int rc = variant == -3 ? gemm_launch_skinny(dtype, EPI_PATCH, p, reinterpret_cast<hipStream_t>(stream), nullptr)
+                               : gemm_launch(dtype, EPI_PATCH, variant, p, reinterpret_cast<hipStream_t>(stream), nullptr);
   if (rc != 0) return fail(PLIPMI_ERR_HIP, "patch gemm launch failed (variant %d, M=%d N=%d K=%d): %s", variant, M, N, K,
                            hipGetErrorString((hipError_t)rc));
   return PLIPMI_OK;

@@ -85,7 +85,8 @@ def gemm_nt_ln(mode: int, a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, 
     """Kernel-level entry (tests) for the LayerNorm-folded epilogues, see include/plipmi.h plipmi_gemm_nt_ln.
     mode 0/1 -> bf16 [M,N]; mode 2 -> (C fp32 updated in place, xb bf16 [M,N], st fp32 [M,N/64,2]); mode 3 -> the same
     update on the split residual stream: ``out`` = (hi 16-bit [M,N], lo uint8 [lo_plane_bytes(M, N)], the blocked 8-bit remainder
-    plane), both updated in place; returns (hi, lo, st)."""
+    plane), both updated in place; returns (hi, lo, st).  variant -3 (the small-M split-K kernel, K % 256 == 0) runs modes 0 .. 3 and
+    refuses mode 4; its mode 3 adds (x + bias) + product like the tiles, its mode 2 x + (product + bias)."""
     lib = _lib.load()
     assert a.dtype in (torch.bfloat16, torch.float16) and w.dtype == a.dtype and a.is_contiguous() and w.is_contiguous()
     code, hdt = _code(a.dtype), a.dtype
@@ -471,7 +472,8 @@ def cls_rows(cls: torch.Tensor, pos: torch.Tensor, x: torch.Tensor, B: int, toke
 
 def gemm_patch(a: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, out: torch.Tensor, K: Optional[int] = None, variant: int = -1) -> torch.Tensor:
     """``plipmi_gemm_patch`` (the EPI_PATCH epilogue): a [B * np, lda], w [N, ldw] (K <= lda, ldw columns used; default all of a's),
-    pos fp32 [np + 1, N] -> token rows img * (np + 1) + 1 + p of ``out`` fp32 [>= B * (np + 1), N]."""
+    pos fp32 [np + 1, N] -> token rows img * (np + 1) + 1 + p of ``out`` fp32 [>= B * (np + 1), N].  variant -3 = the small-M split-K
+    kernel (bf16 / f16, N % 64 == 0, K % 256 == 0; anything else is refused before a launch)."""
     lib = _lib.load()
     assert a.is_cuda and w.is_cuda and a.dtype == w.dtype and a.is_contiguous() and w.is_contiguous()
     _f32(pos, out)

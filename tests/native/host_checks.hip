@@ -311,7 +311,7 @@ static void check_early_returns() {
   REJECTS(plipmi_gemm_nt_ln(1, 0, -1, 4, 128, 128, f, f, f, nullptr, 2, 1e-5f, f, f, f, nullptr), "need the row statistics");
   REJECTS(plipmi_gemm_nt_ln(1, 1, -1, 4, 128, 128, f, f, f, f, 3, 1e-5f, f, f, f, nullptr), "must be even");
   REJECTS(plipmi_gemm_nt_ln(1, 2, -1, 4, 96, 128, f, f, f, f, 2, 1e-5f, f, f, f, nullptr), "need xb_out, st_out");
-  REJECTS(plipmi_gemm_nt_ln(2, 3, -3, 4, 128, 128, f, f, f, f, 2, 1e-5f, f, f, f, nullptr), "no split-plane epilogue");
+  REJECTS(plipmi_gemm_nt_ln(2, 4, -3, 4, 128, 256, f, f, f, f, 2, 1e-5f, f, f, f, nullptr), "the engine re-codes them in enter_block");
   REJECTS(plipmi_attention(3, 0, f, f, 1, 4, 1, 0, nullptr, nullptr), "bad argument");
   REJECTS(plipmi_attention(0, 0, f, nullptr, 1, 4, 1, 0, nullptr, nullptr), "bad argument");
   REJECTS(plipmi_attention_probs(0, f, f, 1, 1025, 1, 0, nullptr, nullptr), "bad argument");
@@ -371,7 +371,10 @@ static void check_early_returns() {
   REJECTS(plipmi_gemm_patch(0, -1, 4, 4, 4, f, 4, f, 4, nullptr, 2, f, nullptr), "null pointer");
   REJECTS(plipmi_gemm_patch(0, -1, 4, 4, 4, f, 4, f, 4, f, 0, f, nullptr), "np = 0");
   REJECTS(plipmi_gemm_patch(0, -1, 4, 4, 4, f, 4, f, 4, f, 3, f, nullptr), "np = 3");
-  REJECTS(plipmi_gemm_patch(0, -3, 4, 4, 4, f, 4, f, 4, f, 2, f, nullptr), "variant -3");
+  REJECTS(plipmi_gemm_patch(0, -3, 4, 64, 256, f, 256, f, 256, f, 2, f, nullptr), "variant -3: the small-M kernel takes 16-bit operands");
+  REJECTS(plipmi_gemm_patch(1, -3, 4, 64, 640, f, 640, f, 640, f, 2, f, nullptr), "K % 256 == 0");      // Kpad of a 14-pixel patch
+  REJECTS(plipmi_gemm_patch(2, -3, 4, 32, 256, f, 256, f, 256, f, 2, f, nullptr), "N % 64 == 0");
+  REJECTS(plipmi_gemm_patch(1, -4, 4, 64, 256, f, 256, f, 256, f, 2, f, nullptr), "variant -4");
   REJECTS(plipmi_gemm_patch_gather(0, f, nullptr, f, f, f, 1, 16, 16, 16, 256, nullptr), "16-bit-engine form");
   REJECTS(plipmi_gemm_patch_gather(1, nullptr, nullptr, f, f, f, 1, 16, 16, 16, 256, nullptr), "exactly one of pixels / tiles");
   REJECTS(plipmi_gemm_patch_gather(1, f, u8, f, f, f, 1, 16, 16, 16, 256, nullptr), "exactly one of pixels / tiles");

@@ -147,9 +147,12 @@ def test_cls_rows_writes_row_zero_of_each_image_only(D, tokens):
 # =====================================================================================================================================
 # (P, H, W, B, N): np = 12 on a floored 3 x 4 grid, B = 30 -> M = 360: every tile height (128 / 160 / 192 / 256 / 320) ends inside an
 # image and leaves a partial last tile; np = 1: CLS and patch rows alternate; P = 14: K = 588 inside lda = ldw = Kpad = 640, the padding
-# columns zero in A and in W as the engine has them
+# columns zero in A and in W as the engine has them; P = 32: K = 3072, M = 42 in one partial tile.
+# The small-M split-K kernel (variant -3, the latency path's patch GEMM; 16-bit types, K % 256 == 0) has 32-row tiles: M = 360 puts
+# their borders inside images and leaves a partial last one, M = 42 one whole and one partial; K = 768 is one pass of its (4, 3) form,
+# K = 3072 two of (8, 3)
 PATCH_SHAPES = {"np12": (16, 52, 72, 30, 256), "np1": (16, 16, 16, 5, 256), "np12_n512": (16, 52, 72, 30, 512),
-                "np12_k588": (14, 44, 58, 30, 256)}
+                "np12_k588": (14, 44, 58, 30, 256), "p32_b7": (32, 64, 96, 7, 256)}
 
 
 def _patch_operands(P, H, W, B, N, dt, seed):
@@ -182,7 +185,10 @@ def _check_token_rows(got, ref, np_, group, case):
 @pytest.mark.parametrize("dname", list(DT))
 def test_patch_epilogue_scatters_patch_rows_to_token_rows(dname, shape):
     """Patch row img * np + p lands in token row img * (np + 1) + 1 + p with position row 1 + p added, on every tile and the naive kernel,
-    against conv2d in float64; for the 16-bit types every tile gives tile 0's bits (test_every_tile_sums_k_in_the_same_order)."""
+    against conv2d in float64; for the 16-bit types every tile gives tile 0's bits (test_every_tile_sums_k_in_the_same_order).
+    The small-M split-K kernel (-3) is held to the same convolution where it applies (its K order differs: no bit claim) and must
+    refuse, before it launches anything, fp32 operands and a K that is no multiple of 256."""
+    from plip_amd._lib import PlipmiError
     from plip_amd.kernel_entries import gemm_patch
     P, H, W, B, N = PATCH_SHAPES[shape]
     dt = DT[dname]
@@ -201,6 +207,16 @@ def test_patch_epilogue_scatters_patch_rows_to_token_rows(dname, shape):
             if first is None:
                 first = got
             assert torch.equal(_bits(got), _bits(first)), f"tile {v} differs from tile 0: {shape} {dname}"
+    out = _sent(B * (np_ + 1) + 2, N, torch.float32)
+    if dt != torch.float32 and a.shape[1] % 256 == 0:
+        gemm_patch(a, w, pos, out, variant=-3)
+        torch.cuda.synchronize()
+        worst = max(worst, _check_token_rows(out.cpu(), ref, np_, f"epi_patch_{dname}", f"{shape}_tile-3"))
+    else:
+        with pytest.raises(PlipmiError, match="16-bit operands" if dt == torch.float32 else "K % 256 == 0"):
+            gemm_patch(a, w, pos, out, variant=-3)
+        torch.cuda.synchronize()
+        assert _untouched(out), f"{shape} {dname}: the refused small-M call wrote"
     assert worst < GEMM_TOL
 
 

@@ -301,7 +301,9 @@ def test_small_m_split_k_gemm(epi, hdt):
     from plip_amd.kernel_entries import gemm_nt
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(31 + epi)
-    for (M, N, K) in [(1, 64, 256), (8, 768, 768), (256, 768, 3072), (256, 2048, 512), (333, 512, 2048)]:
+    # the last three: the split forms (4 waves, 1 block), (4, 3) and (8, 1) on more than one pass of their K loop (5, 3 and 5)
+    for (M, N, K) in [(1, 64, 256), (8, 768, 768), (256, 768, 3072), (256, 2048, 512), (333, 512, 2048),
+                      (33, 128, 1280), (33, 128, 2304), (33, 128, 2560)]:
         a = torch.randn(M, K, generator=g).to(dev).to(hdt)
         w = (torch.randn(N, K, generator=g) / K ** 0.5).to(dev).to(hdt)      # asymmetric operands
         bias = torch.randn(N, generator=g).to(dev)
@@ -313,3 +315,147 @@ def test_small_m_split_k_gemm(epi, hdt):
         if M >= 8:                                  # rows 3..7 alone give the same bits
             y2 = gemm_nt(a[3:8].contiguous(), w, bias, epilogue=epi, variant=-3, out=c0[3:8].clone() if epi == 2 else None)
             assert torch.equal(y2, y[3:8])
+
+
+# ---- the small-M kernel's split-plane epilogue (gemm_skinny.hip EPI_RESID_SPLIT): what the latency path runs out_proj and fc2 with ------------
+# (M, N, K): K = every live split form (waves, blocks per request) on one pass of its K loop and on several -- 256 / 1280 (4, 1),
+# 768 / 2304 (4, 3), 512 / 2560 (8, 1), 1024 / 2048 (8, 2), 1536 / 3072 (8, 3) --, each with an M that ends inside a 32-row tile;
+# M = every row edge of that tile and of the 16-row lo band (48: a whole band whose tile is half dead, 50: a partly live band),
+# each with at least two K
+SMALL_M_SPLIT_SHAPES = [(1, 64, 256), (33, 128, 1280), (31, 128, 768), (50, 64, 2304), (50, 128, 512), (48, 128, 2560),
+                        (33, 768, 1024), (1, 128, 2048), (31, 64, 1536), (50, 768, 3072), (32, 64, 768), (32, 128, 2048),
+                        (48, 64, 1280)]
+SENT = 0xA5
+
+
+def _sentinel(shape, dtype, dev):
+    size = torch.empty((), dtype=dtype).element_size()
+    return torch.full((*shape[:-1], shape[-1] * size), SENT, dtype=torch.uint8, device=dev).view(dtype)
+
+
+def _untouched(t):
+    return bool((t.contiguous().view(torch.uint8) == SENT).all())
+
+
+def _parity(group, case, bound, value):
+    print(f"\nPARITY group={group} case={case} bound={bound:.3e} gpu={value:.3e}")
+
+
+def _run_small_m_split(a, w, bias, hi0, lo0v, M, N):
+    """mode 3 at variant -3 on the first M rows of buffers with two 16-row lo bands of guard rows behind the last live band, every
+    byte that is not a live row's the sentinel.  lo0v = the remainders uint8 [M, N].  -> (hi, lo, st, idx) with the guard rows."""
+    from plip_amd.kernel_entries import gemm_nt_ln_rows, lo_plane_bytes, lo_plane_index
+    dev = a.device
+    Mt = (M + 15) // 16 * 16 + 32
+    idx = lo_plane_index(Mt, N, dev)
+    hi = _sentinel((Mt, N), a.dtype, dev)
+    lo = torch.full((lo_plane_bytes(Mt, N),), SENT, dtype=torch.uint8, device=dev)
+    st = _sentinel((Mt, N // 64, 2), torch.float32, dev)
+    hi[:M] = hi0
+    lo[idx[:M].reshape(-1)] = lo0v.reshape(-1)
+    gemm_nt_ln_rows(3, a, w, bias, None, (hi, lo), st=st, M=M, variant=-3)
+    return hi, lo, st, idx
+
+
+@pytest.mark.parametrize("hdt", list(HALF.values()), ids=list(HALF))
+def test_small_m_split_plane_residual_epilogue(hdt):
+    """test_split_plane_residual_epilogue for the small-M split-K kernel (variant -3).  The big tiles are held to "mode 3 = the host
+    split of mode 2's fp32 result"; here the two forms associate differently -- the split form adds (x + bias) + product like the
+    tiles, the plain forms x + (product + bias) -- so the reference is composed from calls whose arithmetic is known: the raw fp32
+    accumulators v from the kernel's own fp32 twin on C = 0, bias = 0 (0 + (v + 0) = v), then (x0q + bias) + v as two IEEE fp32
+    adds in torch.  Bit for bit: both planes = the host split of that; the plain forms (epilogue 2, mode 2) = x0q + (v + bias).
+    (The twin returns an accumulator of -0 as +0; that changes a sum only where the other addend is -0, which the test excludes by
+    asserting that x0q + bias has no zero.)  Nothing but the live rows is written: guard rows of hi and st, the lo bytes of every
+    band past the last live one AND of the dead rows inside it keep the sentinel (the kernel stores a row's own 8-byte half of a
+    16-byte lo piece).  Rows 3..7 alone give the bits they have inside the larger call."""
+    from plip_amd.kernel_entries import gemm_nt, gemm_nt_ln, join_planes, lo_plane_values, split_planes
+    dev = torch.device("cuda:0")
+    hname = "bf16" if hdt == torch.bfloat16 else "f16"
+    g0 = torch.Generator().manual_seed(303)
+    rel = 2.0 ** -15 if hdt == torch.bfloat16 else 2.0 ** -18      # worst case of the format (test_split_plane_residual_epilogue)
+    worst64, worst_sum, worst_m2, orders_differ = 0.0, 0.0, 0.0, 0
+    for (M, N, K) in SMALL_M_SPLIT_SHAPES:
+        tag = f"{hname} {M}x{N}x{K}"
+        a = torch.randn(M, K, generator=g0).to(dev).to(hdt)
+        w = (torch.randn(N, K, generator=g0) / K ** 0.5).to(dev).to(hdt)
+        bias = torch.randn(N, generator=g0).to(dev)
+        x0 = (torch.randn(M, N, generator=g0) * 3.0 + 11.0).to(dev)
+        x0[:, 7] -= 90.0
+        if M > 1:                                                   # extreme values (row 0 is left out of the statistics check)
+            x0[0, :4] = torch.tensor([0.0, -0.0, 1e-30, -3.0e38] if hdt == torch.bfloat16 else [0.0, 3.0517578125e-05, 6.2e-5, -60000.0], device=dev)
+        hi0, lo0 = split_planes(x0, hdt)
+        x0q = join_planes(hi0, lo0)                                 # the stream value the planes stand for
+        lo0v = lo_plane_values(lo0, M, N).view(torch.uint8)
+        assert ((x0q - x0).abs() <= x0.abs() * rel + 2.0 ** -32).all()
+        # the composed reference
+        v = gemm_nt(a, w, torch.zeros(N, device=dev), epilogue=2, variant=-3, out=torch.zeros(M, N, device=dev))
+        xb = x0q + bias[None, :]
+        assert (xb != 0).all(), tag                                 # no -0 + (-0): the sign of a zero accumulator cannot matter
+        x_ref = xb + v
+        hi, lo, st, idx = _run_small_m_split(a, w, bias, hi0, lo0v, M, N)
+        torch.cuda.synchronize()
+        # (a) the planes, bit for bit
+        want_hi, want_lo = split_planes(x_ref, hdt)
+        bad_hi = int((hi[:M].view(torch.int16) != want_hi.view(torch.int16)).sum())
+        bad_lo = int((lo[idx[:M].reshape(-1)].reshape(M, N).view(torch.int8) != lo_plane_values(want_lo, M, N)).sum())
+        _parity(f"small_m_split_planes_moved_{hname}", f"{M}x{N}x{K}", 0, bad_hi + bad_lo)
+        assert bad_hi == 0 and bad_lo == 0, (tag, bad_hi, bad_lo)
+        # (b) nothing else is written
+        assert _untouched(hi[M:]) and _untouched(st[M:]), f"{tag}: hi / st written past row {M}"
+        dead = lo[idx[M:].reshape(-1)].reshape(-1, N)               # the dead rows of the last live band, then the guard bands
+        hit = (dead != SENT).any(dim=1).nonzero().reshape(-1)
+        assert hit.numel() == 0, f"{tag}: lo rows {[M + int(r) for r in hit[:8]]} written"
+        # (c) the value, the statistics, the float64 update
+        x = join_planes(hi[:M].contiguous(), lo)
+        assert ((x - x_ref).abs() <= x_ref.abs() * rel + 2.0 ** -32).all(), tag
+        r0 = 1 if M > 1 else 0
+        want = _slice_stats(x_ref)[r0:]
+        e_sum = (st[r0:M, :, 0] - want[..., 0]).abs().max().item()
+        e_m2 = ((st[r0:M, :, 1] - want[..., 1]).abs() / want[..., 1].clamp(min=1e-3)).max().item()
+        worst_sum, worst_m2 = max(worst_sum, e_sum), max(worst_m2, e_m2)
+        assert e_sum < 1e-3 and e_m2 < 1e-4, (tag, e_sum, e_m2)
+        ref = x0q.double() + a.double() @ w.double().T + bias.double()
+        err = (x.double() - ref).abs().max().item()
+        assert err < 2e-4 * max(1.0, ref.abs().max().item()), (tag, err)
+        err = (x[r0:].double() - ref[r0:]).abs().max().item() / max(1.0, ref[r0:].abs().max().item())   # ... and without the extreme row, whose magnitude sets that bound
+        worst64 = max(worst64, err)
+        assert err < 2e-4, (tag, err)
+        # (d) the plain forms as the code has them: x + (v + bias), not the split form's order
+        x_plain = x0q + (v + bias[None, :])
+        y2 = gemm_nt(a, w, bias, epilogue=2, variant=-3, out=x0q.clone())
+        x2, xb2, _ = gemm_nt_ln(2, a, w, bias, variant=-3, out=x0q.clone())
+        moved = int((y2.view(torch.int32) != x_plain.view(torch.int32)).sum()) + int((x2.view(torch.int32) != x_plain.view(torch.int32)).sum())
+        _parity(f"small_m_plain_residual_moved_{hname}", f"{M}x{N}x{K}", 0, moved)
+        assert moved == 0 and torch.equal(xb2, x2.to(hdt)), (tag, moved)
+        plain_hi, plain_lo = split_planes(x_plain, hdt)             # what "mode 3 = the split of mode 2's result" would have asked for
+        orders_differ += int((plain_hi.view(torch.int16) != want_hi.view(torch.int16)).sum()) + int((lo_plane_values(plain_lo, M, N) != lo_plane_values(want_lo, M, N)).sum())
+        # (e) rows 3..7 alone
+        if M >= 8:
+            h5, l5, s5, i5 = _run_small_m_split(a[3:8].contiguous(), w, bias, hi0[3:8], lo0v[3:8], 5, N)
+            torch.cuda.synchronize()
+            assert torch.equal(h5[:5].view(torch.int16), hi[3:8].view(torch.int16)) and torch.equal(s5[:5], st[3:8]), tag
+            assert torch.equal(l5[i5[:5].reshape(-1)], lo[idx[3:8].reshape(-1)]), tag
+            assert _untouched(h5[5:]) and _untouched(s5[5:]) and bool((l5[i5[5:].reshape(-1)] == SENT).all()), tag
+    # the bit equality above does tell the two orders apart: their planes differ somewhere on these shapes
+    _parity(f"small_m_plane_elements_the_other_order_moves_{hname}", "13_shapes_at_least", 1, orders_differ)
+    assert orders_differ >= 1
+    _parity(f"small_m_split_vs_float64_{hname}", "13_shapes_rows_without_extremes", 2e-4, worst64)
+    _parity(f"small_m_split_slice_sum_{hname}", "13_shapes", 1e-3, worst_sum)
+    _parity(f"small_m_split_slice_m2_{hname}", "13_shapes", 1e-4, worst_m2)
+
+
+def test_small_m_split_plane_epilogue_refuses_the_other_types_format():
+    """mode 4 (planes written in the other 16-bit type's format) is a big-tile form: the small-M kernel ignores planes_other, so the
+    entry refuses it, and says what the engine does instead; nothing is launched"""
+    from plip_amd._lib import PlipmiError
+    from plip_amd.kernel_entries import gemm_nt_ln_rows, lo_plane_bytes
+    dev = torch.device("cuda:0")
+    M, N, K = 8, 64, 256
+    a, w = torch.zeros(M, K, dtype=torch.bfloat16, device=dev), torch.zeros(N, K, dtype=torch.bfloat16, device=dev)
+    hi = _sentinel((M, N), torch.bfloat16, dev)
+    lo = torch.full((lo_plane_bytes(M, N),), SENT, dtype=torch.uint8, device=dev)
+    st = _sentinel((M, 1, 2), torch.float32, dev)
+    with pytest.raises(PlipmiError, match="re-codes them in enter_block"):
+        gemm_nt_ln_rows(4, a, w, torch.zeros(N, device=dev), None, (hi, lo), st=st, M=M, variant=-3)
+    torch.cuda.synchronize()
+    assert _untouched(hi) and _untouched(lo) and _untouched(st)

@@ -239,12 +239,28 @@ def test_wide_range_layernorm_folded_epilogues(hname, variant, mode):
     assert float((y[rows][:, 1::2] != 0).float().mean()) > 0.4, case
 
 
-@pytest.mark.parametrize("variant", TILES + [-1])
-@pytest.mark.parametrize("hname,mode", [("f16", 3), ("f16", 4), ("bf16", 4)])
+def _small_m_split_ref(a, w, bias, x0q):
+    """What the small-M kernel's split-plane epilogue computes, composed from calls whose arithmetic is known (test_gpu_gemm.py
+    test_small_m_split_plane_residual_epilogue): its raw fp32 accumulators v from the fp32 twin on C = 0, bias = 0 (0 + (v + 0) = v,
+    NaN and inf included), then (x0q + bias) + v as two IEEE fp32 adds.  Mode 2 is no reference at -3: it adds x + (v + bias).
+    (The twin turns an accumulator of -0 into +0, which matters only next to an x0q + bias of -0: asserted absent.)"""
+    from plip_amd.kernel_entries import gemm_nt
+    v = gemm_nt(a, w, torch.zeros(N, device=DEV), epilogue=2, variant=-3, out=torch.zeros(M, N, device=DEV))
+    xb = x0q + bias[None, :]
+    assert not bool(((xb == 0) & torch.signbit(xb)).any())
+    return xb + v
+
+
+# every tile and the cost model's for the three (type, mode) pairs; the small-M kernel has mode 3 only, in both types
+SPLIT_CASES = [(h, m, v) for h, m in (("f16", 3), ("f16", 4), ("bf16", 4)) for v in TILES + [-1]] + [("f16", 3, -3), ("bf16", 3, -3)]
+
+
+@pytest.mark.parametrize("hname,mode,variant", SPLIT_CASES, ids=[f"{h}-{m}-{v}" for h, m, v in SPLIT_CASES])
 def test_wide_range_split_plane_epilogues(hname, mode, variant):
     """the residual update on planes whose values sit at the edges of f16: 65500 carried past 65504 by the update, subnormal entries
     that stay subnormal, and the wide-range update everywhere else -- planes = the host split (of the type the mode writes) of the
-    plain-array epilogue's fp32 result, bit for bit, as test_gpu_gemm.py requires at ordinary magnitudes"""
+    plain-array epilogue's fp32 result, bit for bit, as test_gpu_gemm.py requires at ordinary magnitudes (variant -3: of the composed
+    reference _small_m_split_ref, the small-M kernel's plain-array epilogue adding in another order)"""
     from plip_amd.kernel_entries import gemm_nt_ln, join_planes, lo_plane_values, split_planes
     hdt, d, g = HALF[hname], _operands(hname), _dev(hname)
     odt = hdt if mode == 3 else (torch.bfloat16 if hdt == torch.float16 else torch.float16)
@@ -257,7 +273,10 @@ def test_wide_range_split_plane_epilogues(hname, mode, variant):
         x0[tiny] = torch.randn(int(tiny.sum()), generator=g0) * 2.0 ** -16
     hi0, lo0 = split_planes(x0.to(DEV), hdt)
     x0q = join_planes(hi0, lo0)
-    x_ref, _, _ = gemm_nt_ln(2, g["a"], g["w"], g["bias"], variant=variant, out=x0q.clone())
+    if variant == -3:
+        x_ref = _small_m_split_ref(g["a"], g["w"], g["bias"], x0q)
+    else:
+        x_ref, _, _ = gemm_nt_ln(2, g["a"], g["w"], g["bias"], variant=variant, out=x0q.clone())
     hi, lo, st = gemm_nt_ln(mode, g["a"], g["w"], g["bias"], variant=variant, out=(hi0.clone(), lo0.clone()))
     torch.cuda.synchronize()
     hi = hi.view(odt)
@@ -299,7 +318,7 @@ EPIS = ["e0", "e1", "e2", "ln0", "ln1", "ln2", "ln3"]
 def _epis(dname, variant):
     out = ["e0", "e1", "e2"]
     if dname != "f32" and variant != -2:                                  # the naive checker has no LayerNorm-folded epilogue
-        out += ["ln0", "ln1", "ln2"] + (["ln3"] if variant != -3 else [])  # the small-M kernel has no split-plane epilogue
+        out += ["ln0", "ln1", "ln2", "ln3"]                                # (-3 too: the latency path's out_proj and fc2 run its ln3)
     return out
 
 
@@ -416,7 +435,8 @@ def test_a_non_finite_operand_stays_in_its_row_or_column(dname, variant):
                     else:
                         assert torch.equal(inner[~nan].double(), want[~nan]), (tag, name)
                 if "hi" in got:                                            # ... and the planes are still the host split of the plain-array result
-                    x_ref = _run("ln2", dname, variant, a, w, dv)["c"][:M]
+                    # (the small-M kernel: of the composed reference -- its plain-array form adds in another order)
+                    x_ref = _small_m_split_ref(a, w, dv["bias"], dv["c0"]) if variant == -3 else _run("ln2", dname, variant, a, w, dv)["c"][:M]
                     want_hi, want_lo = split_planes(x_ref, dt)
                     assert _same_or_both_nan(got["hi"][:M], want_hi), tag
                     ok = ~torch.isnan(x_ref)
