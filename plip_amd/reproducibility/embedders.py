@@ -27,7 +27,7 @@ class CLIPEmbedder:
                  backbone: str = "", tokenizer: Optional[Callable] = None, ragged_resize: bool = False):
         """``ragged_resize`` (extension, only without a ``preprocess`` of the caller's): images are not preprocessed one by one in
         host Pillow -- uint8 / PIL batches are resized, cropped (torchvision's rule, as ``_transform`` does) and normalised on the GPU,
-        whatever their sizes (``plip.prepare_routed_batch``: native tiles / one size / differing sizes; float inputs and images
+        whatever their sizes (``image_routes.prepare_routed_batch``: native tiles / one size / differing sizes; float inputs and images
         shrunk more than 64 x keep the host path).  Off: every image goes through ``preprocess`` as before."""
         self.model = model
         self.ragged_resize = bool(ragged_resize) and preprocess is None
@@ -90,15 +90,15 @@ class CLIPEmbedder:
         return torch.cat(out).cpu().numpy()
 
     def _embed_images_routed(self, images: list, num_workers, batch_size) -> np.ndarray:
-        """``ragged_resize``: every batch is decoded and routed on the host (``plip.prepare_routed_batch``) and resized, cropped,
+        """``ragged_resize``: every batch is decoded and routed on the host (``image_routes.prepare_routed_batch``) and resized, cropped,
         normalised and encoded on the GPU, inside the lane it runs on; with ``num_workers > 1`` one batch ahead on a thread pool."""
-        from ..plip import _PinnedPair, consume_routed_batch, prepare_routed_batch
+        from ..image_routes import PinnedPair, consume_routed_batch, prepare_routed_batch
         eng, n_px, crop = self.model.engine, self.model.config.image_size, "torchvision"
         if not images:
             return np.zeros((0, self.model.config.projection_dim), np.float32)
         if num_workers and num_workers > 1:
             from ..pipeline import run_batches
-            pinned = _PinnedPair()
+            pinned = PinnedPair()
             step = max(1, min(int(batch_size), eng.max_batch))
             outs = run_batches(images, step, None, lambda tag, t, e=eng: consume_routed_batch(e, tag, t, crop, normalize=True),
                                device=eng.device, num_workers=num_workers,

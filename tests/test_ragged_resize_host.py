@@ -148,6 +148,10 @@ class RecordingEngine(Hh.OracleEngine):
     def lane_loop(self):
         yield lambda fn: fn(self)
 
+    def at_resolution(self, height, width):      # encode_images(image_size=N): the stand-in serves its own size only
+        assert (height, width) == (self.cfg.image_size, self.cfg.image_size)
+        return self
+
 
 @pytest.fixture(scope="module")
 def tiny():
@@ -183,14 +187,26 @@ def _calls(engine):
     return out
 
 
+def _encode_both_ways(ours, eng, seq, batch_size):
+    """``encode_images(seq)`` at the checkpoint's resolution and with ``image_size=`` that very size: ONE loop serves both, so the
+    stand-in records the same calls (shapes and crop rules included) and the arrays are equal.  -> the embeddings, the calls"""
+    eng.calls.clear()
+    at = ours.encode_images(seq, batch_size=batch_size, image_size=N)
+    calls_at = list(eng.calls)
+    eng.calls.clear()
+    got = ours.encode_images(seq, batch_size=batch_size)
+    assert eng.calls == calls_at and len(calls_at) > 0
+    np.testing.assert_array_equal(got, at)
+    return got, _calls(eng)
+
+
 def test_plip_routing_with_ragged_resize(tiny):
     from plip_amd.preprocess import preprocess_images
     cfg, sd = tiny
     ours, eng = _plip(tiny, True)
     mixed = [_image(h, w) for h, w in SIZES[:12]]
     # chunks of 4 of differing sizes: coalesced into ragged calls of up to max_batch = 8 images, in order
-    got = ours.encode_images(mixed, batch_size=4)
-    calls = _calls(eng)
+    got, calls = _encode_both_ways(ours, eng, mixed, 4)
     assert [c[0] for c in calls] == ["resize_crop_ragged", "encode_image_u8"] * 2
     assert calls[0][1] == tuple(SIZES[:8]) and calls[2][1] == tuple(SIZES[8:12]) and calls[0][2] == calls[2][2] == "hf"
     host, heng = _plip(tiny, False)
@@ -201,20 +217,18 @@ def test_plip_routing_with_ragged_resize(tiny):
     tiles = [_image(N, N, s) for s in range(4)]
     same = [_image(96, 130, s) for s in range(4)]
     seq = tiles + mixed[4:8] + same + mixed[8:12]
-    eng.calls.clear()
-    got = ours.encode_images(seq, batch_size=4)
-    # (the one-size chunk is resized when it is routed, i.e. before the pending ragged images are flushed, as on the existing routes)
-    assert [c[0] for c in _calls(eng)] == ["encode_image_u8", "resize_crop_u8", "resize_crop_ragged", "encode_image_u8", "encode_image_u8",
-                                          "resize_crop_ragged", "encode_image_u8"]
+    got, calls = _encode_both_ways(ours, eng, seq, 4)
+    # (every resize is enqueued in the flush that encodes its rows: the pending ragged images leave when the one-size chunk arrives,
+    # and that chunk is resized when IT is flushed, directly in front of its own encode)
+    assert [c[0] for c in calls] == ["encode_image_u8", "resize_crop_ragged", "encode_image_u8", "resize_crop_u8", "encode_image_u8",
+                                     "resize_crop_ragged", "encode_image_u8"]
     want = host.encode_images(seq, batch_size=4)
     np.testing.assert_allclose(got, want, rtol=0, atol=2e-6)
     # an image over the ratio limit and a float image keep the host path, one by one, and the order is kept
     big = np.random.RandomState(5).randint(0, 256, (N * 64 + 6, N * 64 + 1, 3), dtype=np.uint8)
     flt = _image(50, 70)[..., 0].astype(np.float32)          # (a 2-D float array is Pillow's mode F: the host path takes it)
     seq = [mixed[1], big, mixed[2], mixed[3], flt]
-    eng.calls.clear()
-    got = ours.encode_images(seq, batch_size=5)
-    calls = _calls(eng)
+    got, calls = _encode_both_ways(ours, eng, seq, 5)
     assert [c[0] for c in calls] == ["resize_crop_ragged", "encode_image_u8", "encode_image", "resize_crop_ragged", "encode_image_u8",
                                      "encode_image"]
     assert calls[0][1] == (SIZES[1],) and calls[3][1] == (SIZES[2], SIZES[3]) and calls[2][1][0] == 1 and calls[5][1][0] == 1
@@ -236,12 +250,16 @@ def test_plip_routing_with_ragged_resize(tiny):
 
 
 def test_default_routes_are_unchanged(tiny):
-    """ragged_resize=False -- and a PLIP object that never heard of the keyword -- record the calls the host loops made before the
-    route existed: a list of differing sizes goes through host Pillow, and the stand-in of tests/helpers.py (which has no ragged
-    entry) keeps working."""
+    """ragged_resize=False -- and a PLIP object that never heard of the keyword -- take the routes and return the arrays the host loops
+    did before the ragged route existed: a list of differing sizes goes through host Pillow, and the stand-in of tests/helpers.py
+    (which has no ragged entry, no lanes and no ``at_resolution``) keeps working.  What moved: the direct loop used to resize a
+    one-size chunk when it ROUTED it, ahead of the pending batches; now, as the pipelined loop always did, the resize is enqueued in
+    the flush that encodes its rows, so both loops record the same sequence."""
     from plip_amd.plip import PLIP
     cfg, sd = tiny
     seq = [_image(h, w) for h, w in SIZES[:4]] + [_image(N, N, s) for s in range(4)] + [_image(96, 130, s) for s in range(4)]
+    # host pixels flushed when the native tiles arrive, the staged tiles when the one-size chunk arrives, then its resize and encode
+    want_calls = [("encode_image", 4), ("encode_image_u8", 4), ("resize_crop_u8", 4), ("encode_image_u8", 4)]
     outs = []
     for attr in (False, None):
         model = Hh.oracle_model(cfg, sd)
@@ -252,16 +270,23 @@ def test_default_routes_are_unchanged(tiny):
         if attr is not None:
             ours.ragged_resize = attr
         a = ours.encode_images(seq, batch_size=4)
-        # host pixels flushed when the native tiles arrive; the one-size chunk resized at once, then the staged tiles, then its own
-        assert [(c[0], c[1][0]) for c in _calls(model.engine)] == [("encode_image", 4), ("resize_crop_u8", 4), ("encode_image_u8", 4),
-                                                                   ("encode_image_u8", 4)]
+        assert [(c[0], c[1][0]) for c in _calls(model.engine)] == want_calls
         model.engine.calls.clear()
         b = ours.encode_images(seq, batch_size=4, num_workers=2)
-        assert [(c[0], c[1][0]) for c in _calls(model.engine)] == [("encode_image", 4), ("encode_image_u8", 4), ("resize_crop_u8", 4),
-                                                                   ("encode_image_u8", 4)]
+        assert [(c[0], c[1][0]) for c in _calls(model.engine)] == want_calls
         np.testing.assert_allclose(a, b, rtol=0, atol=2e-6)
         outs.append(a)
     np.testing.assert_array_equal(outs[0], outs[1])
+    # image_size= runs the same loop: the same calls on an engine that has ``at_resolution``, and the same arrays
+    ours, eng = _plip(tiny, False)
+    got, calls = _encode_both_ways(ours, eng, seq, 4)
+    assert [(c[0], c[1][0]) for c in calls] == want_calls
+    np.testing.assert_array_equal(got, outs[0])
+    # one-size chunks of two sizes share a flush: each size resized by itself inside it, the eight tiles encoded together
+    other = [_image(80, 72, s) for s in range(4)]
+    got, calls = _encode_both_ways(ours, eng, seq[8:] + other, 4)
+    assert [c[:2] for c in calls] == [("resize_crop_u8", (4, 96, 130, 3)), ("resize_crop_u8", (4, 80, 72, 3)), ("encode_image_u8", (8, N, N, 3))]
+    np.testing.assert_allclose(got, np.concatenate([outs[0][8:], ours.encode_images(other, batch_size=4)]), rtol=0, atol=2e-6)
 
 
 def test_plip_class_default_is_off():
