@@ -48,6 +48,9 @@ extern "C" {
 
 #define PLIPMI_VERSION 412 /* (plipmi_tower_shape / plipmi_encode_tower_outputs and plipmi_clone_resolution are new entries, the
                             * config struct is unchanged: the number stays, an existing test pins it)
+                            * (PLIPMI_FLAG_VISION_GELU / PLIPMI_FLAG_TEXT_GELU are new bits of `flags`: the struct and the number stay
+                            * again; a library built before them refuses the bits with its "unknown bits in plipmi_config.flags"
+                            * error, it never runs a gelu checkpoint with QuickGELU)
                             * 0.4.1: `pass_batch` appended to the config struct -- a 0.4.0 caller's shorter struct means 0 = automatic;
                             * 0.4.0: plipmi_config starts with `struct_size` (the struct can grow at its tail without breaking
                             * callers compiled against an older header); test / A-B hooks moved to plipmi_test.h
@@ -72,12 +75,16 @@ enum {
                                         * does, instead of on the pooled row of each sample only */
   PLIPMI_FLAG_PACK_CAPTIONS = 4,       /* start with caption packing on (plipmi_set_text_packing) */
   PLIPMI_FLAG_VALU_ATTENTION = 8,      /* exact-fp32 VALU attention kernel instead of the MFMA kernels (A/B measurements) */
-  PLIPMI_FLAG_TEXT_TOWER_F16 = 16      /* bf16 engine only: the TEXT tower's operands (weights, activations, its plane of
+  PLIPMI_FLAG_TEXT_TOWER_F16 = 16,     /* bf16 engine only: the TEXT tower's operands (weights, activations, its plane of
                                         * the residual stream) are IEEE half instead of bf16.  The text side carries
                                         * 3.2x the image side's embedding error in bf16 (operand rounding of the weights,
                                         * coherent over a caption's tokens) and 40 % of the step's time:
                                         * half precision there buys most of the f16 engine's accuracy for a third of
                                         * its cost.  The image tower stays bf16. */
+  PLIPMI_FLAG_VISION_GELU = 32,        /* the vision tower's MLP activation is the exact (erf) GELU of HF hidden_act = "gelu",
+                                        * 0.5 x (1 + erf(x / sqrt 2)), instead of QuickGELU (hidden_act = "quick_gelu", the default):
+                                        * open_clip / LAION-trained checkpoints.  Every dtype and every path of the engine. */
+  PLIPMI_FLAG_TEXT_GELU = 64           /* the same for the text tower; the two towers choose independently */
 };
 
 /* towers, for plipmi_debug_hidden */

@@ -84,6 +84,15 @@ int plipmi_gemm_nt_traced(int dtype, int epilogue, int variant, int M, int N, in
 int plipmi_gemm_nt_ln(int dtype, int mode, int variant, int M, int N, int K, const void* A, const void* W, const float* bias,
                       const float* stats, int ns, float eps, void* C, void* xb_out, float* st_out, void* stream);
 
+/* Kernel-level entry for the exact-GELU epilogues (gemm.h EPI_BIAS_GELU / EPI_GELU_LN; the fc1 GEMM of a hidden_act = "gelu" tower):
+ *   ln 0: C(T)   = gelu(A.W^T + bias[n])             every dtype; variant as plipmi_gemm_nt (-1, a tile, -2 the naive checker, and
+ *                                                     -3 the small-M split-K kernel for the 16-bit types, K % 256 == 0)
+ *   ln 1: C(h16) = gelu(rstd[m] * A.W^T + bias[n])   16-bit types only, stats / ns / eps as mode 1 of plipmi_gemm_nt_ln; variants -1,
+ *                                                     a tile, -3 (the naive checker has no LayerNorm-folded form)
+ * gelu(y) = 0.5 y (1 + erf(y / sqrt 2)); stats may be NULL and ns 0 for ln 0. */
+int plipmi_gemm_nt_gelu(int dtype, int ln, int variant, int M, int N, int K, const void* A, const void* W, const float* bias,
+                        const float* stats, int ns, float eps, void* C, void* stream);
+
 /* Kernel-level entry for the text tower's fused kernel (csrc/qkv_attention.hip): LayerNorm-folded q/k/v projection (mode 0 of
  * plipmi_gemm_nt_ln with N = 3 * 64 H) with the attention in its epilogue, out [B*S, 64 H] -- bit-identical to
  * plipmi_gemm_nt_ln(mode 0) followed by plipmi_attention(impl 1).  dtype PLIPMI_BF16 | PLIPMI_F16, 65 <= S <= 80, ns = H.

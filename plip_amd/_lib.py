@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libplipmi.so")
 F32, BF16, F16 = 0, 1, 2
 # plipmi_config.flags
 FLAG_SEPARATE_LAYERNORM, FLAG_DENSE_LAST_BLOCK, FLAG_PACK_CAPTIONS, FLAG_VALU_ATTENTION, FLAG_TEXT_TOWER_F16 = 1, 2, 4, 8, 16
+FLAG_VISION_GELU, FLAG_TEXT_GELU = 32, 64     # a tower's MLP activation is the erf GELU (HF hidden_act "gelu"), not QuickGELU
 VISION, TEXT = 0, 1
 
 
@@ -110,6 +111,7 @@ TEST_SYMBOLS = {
     "plipmi_gemm_patch_gather": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "plipmi_gemm_nt_ln_rows": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "plipmi_attention_packed": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "plipmi_gemm_nt_gelu": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp]),
 }
 # every symbol include/plipmi.h declares (the product interface): (restype, argtypes)
 SYMBOLS = {

@@ -19,7 +19,10 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 BUILD = os.path.join(CSRC, "build")
 LIB = os.path.join(CSRC, "libplipmi.so")
 SOURCES = ["engine.hip", "towers.hip", "heads.hip", "test_entries.hip", "gemm.hip", "gemm_f32.hip", "gemm_bf16.hip", "gemm_f16.hip", "gemm_skinny.hip",
-           "tower_kernels.hip", "attention.hip", "attention_mfma.hip", "qkv_attention.hip", "attention_probs.hip", "probe.hip", "resize_ragged.hip", "attention_summary.hip", "head_kernels.hip", "setup_kernels.hip"]
+           "tower_kernels.hip", "attention.hip", "attention_mfma.hip", "qkv_attention.hip", "attention_probs.hip", "probe.hip", "resize_ragged.hip", "attention_summary.hip", "head_kernels.hip", "setup_kernels.hip",
+           # the exact-GELU epilogues: units of their own, behind everything that existed (the other units' code objects and their
+           # places in the link order are those of a build without them)
+           "gemm_gelu_f32.hip", "gemm_gelu_bf16.hip", "gemm_gelu_f16.hip", "gemm_skinny_gelu.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-Wno-unused-value"]
 

@@ -14,6 +14,10 @@ import math
 from dataclasses import dataclass
 
 
+# the MLP activations the engine has kernels for (HF ``hidden_act`` names)
+HIDDEN_ACTS = ("quick_gelu", "gelu")
+
+
 @dataclass(frozen=True)
 class PlipConfig:
     # vision tower (ViT)
@@ -38,6 +42,10 @@ class PlipConfig:
     eos_token_id: int = 49407
     bos_token_id: int = 49406
     logit_scale_init: float = 2.6592
+    # MLP activation of each tower, HF ``hidden_act``: "quick_gelu" (x * sigmoid(1.702 x): OpenAI CLIP, PLIP) or "gelu" (the erf
+    # form 0.5 x (1 + erf(x / sqrt 2)): open_clip / LAION-trained checkpoints).  configuration_clip.py keeps one per tower.
+    v_hidden_act: str = "quick_gelu"
+    t_hidden_act: str = "quick_gelu"
 
     # ---- derived -----------------------------------------------------
     @property
@@ -71,6 +79,9 @@ class PlipConfig:
         for name in ("v_width", "v_mlp", "t_width", "t_mlp"):
             if getattr(self, name) % 128:
                 raise ValueError(f"{name} must be a multiple of 128 (GEMM tile)")
+        for name in ("v_hidden_act", "t_hidden_act"):
+            if getattr(self, name) not in HIDDEN_ACTS:
+                raise ValueError(f"{name} = {getattr(self, name)!r}: the engine has kernels for {' and '.join(map(repr, HIDDEN_ACTS))}")
         # 3*patch^2 need not be a multiple of the GEMM K tile: the unfold kernel
         # zero-pads the patch rows (ViT-L/14: 588 -> 640).
 
@@ -108,6 +119,17 @@ class PlipConfig:
     def replace(self, **kw) -> "PlipConfig":
         return dataclasses.replace(self, **kw)
 
+    def with_hidden_act(self, hidden_act) -> "PlipConfig":
+        """This config with the caller's ``hidden_act`` folded in: None keeps it, one name sets both towers, a
+        ``(vision, text)`` pair each of them (None inside a pair keeps that tower's).  Validated here, so that a wrong
+        name is refused before any engine is built."""
+        if hidden_act is None:
+            return self
+        v, t = (hidden_act, hidden_act) if isinstance(hidden_act, str) else tuple(hidden_act)
+        cfg = self.replace(v_hidden_act=self.v_hidden_act if v is None else v, t_hidden_act=self.t_hidden_act if t is None else t)
+        cfg.validate()
+        return cfg
+
 
 # ``PC_CLIP_ARCH`` names used by reproducibility/config_example.env:4 and
 # OpenAI-clip's ``clip.load`` (reproducibility/embedders/factory.py:21).
@@ -143,7 +165,16 @@ def from_hf_config(hf) -> PlipConfig:
     """Build a PlipConfig from a ``transformers.CLIPConfig`` (or its dict)."""
     d = hf if isinstance(hf, dict) else hf.to_dict()
     t, v = d["text_config"], d["vision_config"]
+    # absent = HF's own default (configuration_clip.py: hidden_act="quick_gelu"); any other name than the two the engine has
+    # kernels for is refused here, never ignored: the shapes would load and the embeddings would be wrong
+    acts = {}
+    for field, sub_cfg, where in (("v_hidden_act", v, "vision_config"), ("t_hidden_act", t, "text_config")):
+        acts[field] = sub_cfg.get("hidden_act") or "quick_gelu"
+        if acts[field] not in HIDDEN_ACTS:
+            raise ValueError(f"{where}.hidden_act = {acts[field]!r} ({field}): the engine has kernels for "
+                             f"{' and '.join(map(repr, HIDDEN_ACTS))}")
     return PlipConfig(
+        **acts,
         image_size=v["image_size"], patch_size=v["patch_size"], v_width=v["hidden_size"],
         v_layers=v["num_hidden_layers"], v_heads=v["num_attention_heads"],
         v_mlp=v["intermediate_size"], vocab_size=t["vocab_size"],

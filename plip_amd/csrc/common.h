@@ -250,4 +250,31 @@ template <bool kAccurate> __device__ __forceinline__ float quick_gelu(float x) {
   else return x * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * x));
 }
 
+// GELU, the erf form of hidden_act = "gelu": 0.5 x (1 + erf(x / sqrt 2)) = x Phi(x)  (transformers/activations.py GELUActivation ->
+// torch.nn.functional.gelu)
+// fp32 engine: the formula as torch evaluates it, with the device library's erff.
+// 16-bit engines: x Phi(x) = max(x, 0) - |x| Q(|x|) with the upper tail Q(a) = 1 - Phi(a) from Abramowitz & Stegun 26.2.17,
+//   Q(a) = exp(-a^2 / 2) (c1 t + c2 t^2 + ... + c5 t^5),  t = 1 / (1 + 0.2316419 a),  |error| < 7.5e-8 for every a >= 0
+// (1 / sqrt(2 pi) folded into the c's): one v_rcp_f32, one v_exp_f32 and twelve plain VALU operations per element, no branch.
+// Written on the TAIL, so nothing cancels on the negative side: the result's error is |x| times an ABSOLUTE 1e-7, against the
+// half ulp of f16 at x = -3 (Q = 1.35e-3) of 6.6e-7 |x|, and beyond -3 against the 4.8e-7 |x| that fp32 `1 + erf` itself loses
+// ("Exact GELU").  |x| is cut at 16 before it is squared and multiplied back: Q(16) is 0 in fp32 (exp2(-184)), so every
+// x <= -16, -inf included, gives -0 * ... = +-0 and never inf * 0; +inf stays +inf.  max(x, 0) is the NaN-propagating maximum:
+// a NaN pre-activation comes out as NaN, as it does from QuickGELU.
+template <bool kAccurate> __device__ __forceinline__ float erf_gelu(float x) {
+  if constexpr (kAccurate) {
+    return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
+  } else {
+    const float a = fminf(fabsf(x), 16.0f);
+    const float t = __builtin_amdgcn_rcpf(fmaf(0.2316419f, a, 1.0f));
+    const float e = __builtin_amdgcn_exp2f((a * a) * -0.72134752044448170368f);   // exp(-a^2 / 2)
+    float q = fmaf(t, 0.5307027145f, -0.7265760135f);
+    q = fmaf(t, q, 0.7107068705f);
+    q = fmaf(t, q, -0.1422483683f);
+    q = fmaf(t, q, 0.1274147959f);
+    q = (q * t) * e;
+    return fmaf(-a, q, __builtin_elementwise_maximum(x, 0.0f));
+  }
+}
+
 }  // namespace plipmi

@@ -34,10 +34,13 @@ enum Epilogue : int {
   // an 8-bit remainder -- the stream at 16 (bf16) / 19 (f16) significand bits, its hi plane IS the next GEMM's A operand, and the
   // epilogue moves 6 bytes per element (3 in, 3 out) instead of the 10 of EPI_RESID_EMIT (which writes fp32 and a separate 16-bit copy).
   EPI_RESID_SPLIT = 8, // {hi,lo} += acc + bias[n] (xb_out = hi, lo_io = lo);  st[m, n/64] = {sum, M2}
-  EPI_COUNT = 9
+  // The exact (erf) GELU of hidden_act = "gelu" towers (common.h erf_gelu), appended so that the numbers above keep their values:
+  EPI_BIAS_GELU = 9,   // C(T)   = gelu(acc + bias[n])
+  EPI_GELU_LN = 10,    // C(bf16) = gelu(rstd[m] * acc + c2[n])            (LN2 -> fc1)
+  EPI_COUNT = 11
 };
-constexpr bool epi_is_ln(int e) { return e == EPI_BIAS_LN || e == EPI_QGELU_LN; }
-constexpr bool epi_is_colwise(int e) { return e == EPI_BIAS || e == EPI_BIAS_QGELU || epi_is_ln(e); }
+constexpr bool epi_is_ln(int e) { return e == EPI_BIAS_LN || e == EPI_QGELU_LN || e == EPI_GELU_LN; }
+constexpr bool epi_is_colwise(int e) { return e == EPI_BIAS || e == EPI_BIAS_QGELU || e == EPI_BIAS_GELU || epi_is_ln(e); }
 constexpr bool epi_is_resid(int e) { return e == EPI_BIAS_RESID || e == EPI_RESID_EMIT || e == EPI_RESID_SPLIT; }
 constexpr bool epi_emits_stats(int e) { return e == EPI_RESID_EMIT || e == EPI_RESID_SPLIT; }
 

@@ -90,7 +90,7 @@ int gemm_default_variant(int dtype, int M, int N, int K) {
 }
 
 static const char* kEpiNames[EPI_COUNT] = {"bias", "bias_qgelu", "bias_resid", "scale", "patch", "ln_bias", "ln_qgelu",
-                                           "resid_emit", "resid_split"};
+                                           "resid_emit", "resid_split", "bias_gelu", "ln_gelu"};
 
 int gemm_launch(int dtype, int epi, int variant, const GemmParams& p, hipStream_t stream, const char** kernel_name) {
   if (variant == -1) variant = gemm_default_variant(dtype, p.M, p.N, p.K);
@@ -112,7 +112,8 @@ int gemm_launch(int dtype, int epi, int variant, const GemmParams& p, hipStream_
   } else if (p.N % 4 != 0) {
     return (int)hipErrorInvalidValue;
   }
-  GemmLaunchFn fn = dtype == 1 ? gemm_get_bf16(variant, epi) : dtype == 2 ? gemm_get_f16(variant, epi) : gemm_get_f32(variant, epi);
+  GemmLaunchFn fn = epi_is_gelu(epi) ? (dtype == 1 ? gemm_get_gelu_bf16(variant, epi) : dtype == 2 ? gemm_get_gelu_f16(variant, epi) : gemm_get_gelu_f32(variant, epi))
+                                     : (dtype == 1 ? gemm_get_bf16(variant, epi) : dtype == 2 ? gemm_get_f16(variant, epi) : gemm_get_f32(variant, epi));
   if (!fn) return (int)hipErrorInvalidValue;
   GemmParams pr = p;
   if (variant >= 0) {

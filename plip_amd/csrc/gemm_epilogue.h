@@ -37,6 +37,9 @@ struct EpilogueOp {
       if constexpr (EPI == EPI_BIAS_QGELU) {
         v0 = quick_gelu<kAccurate>(v0); v1 = quick_gelu<kAccurate>(v1);
         v2 = quick_gelu<kAccurate>(v2); v3 = quick_gelu<kAccurate>(v3);
+      } else if constexpr (EPI == EPI_BIAS_GELU) {
+        v0 = erf_gelu<kAccurate>(v0); v1 = erf_gelu<kAccurate>(v1);
+        v2 = erf_gelu<kAccurate>(v2); v3 = erf_gelu<kAccurate>(v3);
       }
       store4(reinterpret_cast<OutT*>(p.C) + (size_t)m * p.ldc + n0, v0, v1, v2, v3);
     } else if constexpr (epi_is_resid(EPI)) {
@@ -53,7 +56,7 @@ struct EpilogueOp {
 };
 
 // The column-wise 16-bit epilogue's arithmetic on four accumulator values of one row, the same for both MFMA layouts:
-// y = [rstd *] c + bias, [QuickGELU], rounded to the output type.
+// y = [rstd *] c + bias, [QuickGELU / GELU], rounded to the output type.
 template <typename OutT, int EPI>
 __device__ __forceinline__ typename half_traits<OutT>::x4 finish_colwise(float c0, float c1, float c2, float c3, float rs, const float4 bias) {
   float v0, v1, v2, v3;
@@ -66,6 +69,9 @@ __device__ __forceinline__ typename half_traits<OutT>::x4 finish_colwise(float c
   if constexpr (EPI == EPI_BIAS_QGELU || EPI == EPI_QGELU_LN) {
     v0 = quick_gelu<false>(v0); v1 = quick_gelu<false>(v1);
     v2 = quick_gelu<false>(v2); v3 = quick_gelu<false>(v3);
+  } else if constexpr (EPI == EPI_BIAS_GELU || EPI == EPI_GELU_LN) {
+    v0 = erf_gelu<false>(v0); v1 = erf_gelu<false>(v1);
+    v2 = erf_gelu<false>(v2); v3 = erf_gelu<false>(v3);
   }
   return {from_f32<OutT>(v0), from_f32<OutT>(v1), from_f32<OutT>(v2), from_f32<OutT>(v3)};
 }

@@ -1,0 +1,6 @@
+// bf16 instantiations of the NT GEMM's exact-GELU epilogues (gemm.h EPI_BIAS_GELU / EPI_GELU_LN: the fc1 GEMM of a
+// hidden_act = "gelu" tower), in a unit of their own: gemm_bf16.hip's code object is the same with and without them.
+#include "gemm_inst.h"
+namespace plipmi {
+GemmLaunchFn gemm_get_gelu_bf16(int variant, int epi) { return gemm_gelu_pick<bf16_t>(variant, epi); }
+}  // namespace plipmi

@@ -97,6 +97,21 @@ struct GemmTable {
   }
 };
 
+// The exact-GELU kinds (EPI_BIAS_GELU / EPI_GELU_LN) of the same tiles, instantiated in translation units of their own
+// (gemm_gelu_f32.hip / gemm_gelu_bf16.hip / gemm_gelu_f16.hip): the code objects of the units above do not change with them.
+template <typename T>
+GemmLaunchFn gemm_gelu_pick(int variant, int epi) {
+  switch (epi) {
+    case EPI_BIAS_GELU: return GemmTable<T>::template pick<EPI_BIAS_GELU>(variant);
+    case EPI_GELU_LN: return GemmTable<T>::template pick<EPI_GELU_LN>(variant);
+    default: return nullptr;
+  }
+}
+constexpr bool epi_is_gelu(int e) { return e == EPI_BIAS_GELU || e == EPI_GELU_LN; }
+GemmLaunchFn gemm_get_gelu_f32(int variant, int epi);
+GemmLaunchFn gemm_get_gelu_bf16(int variant, int epi);
+GemmLaunchFn gemm_get_gelu_f16(int variant, int epi);
+
 GemmLaunchFn gemm_get_f32(int variant, int epi);
 GemmLaunchFn gemm_get_bf16(int variant, int epi);
 GemmLaunchFn gemm_get_f16(int variant, int epi);

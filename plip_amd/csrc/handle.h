@@ -179,6 +179,10 @@ struct TowerModel {
   // bf16's operand rounding costs the embeddings most -- DESIGN.md section 2.1), the rest on the tower's type.
   int lead_f16 = 0;
   int layer_dtype(int l) const { return l < lead_f16 ? PLIPMI_F16 : dtype; }
+  // MLP activation of this tower's blocks: QuickGELU (HF hidden_act "quick_gelu"), or the exact erf GELU ("gelu";
+  // PLIPMI_FLAG_VISION_GELU / PLIPMI_FLAG_TEXT_GELU) -- the fc1 GEMM's epilogue kind, plain and LayerNorm-folded
+  bool gelu = false;
+  int fc1_epi(bool ln_folded) const { return ln_folded ? (gelu ? EPI_GELU_LN : EPI_QGELU_LN) : (gelu ? EPI_BIAS_GELU : EPI_BIAS_QGELU); }
   std::vector<LayerW> layers;
   // head of the tower: the LayerNorm in front of the projection, the projection [P, D] fp32 (the HF layout, NT GEMM operand)
   // and its transpose [D, P] (the fused pool_head kernel's)

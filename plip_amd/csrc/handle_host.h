@@ -36,7 +36,7 @@ inline int validate_config(const plipmi_config* cfg, plipmi_config* g_out) {
   if (!valid_dtype(g.compute_dtype))
     return fail(PLIPMI_ERR_INVALID, "compute_dtype must be PLIPMI_F32, PLIPMI_BF16 or PLIPMI_F16");
   if (g.flags & ~(PLIPMI_FLAG_SEPARATE_LAYERNORM | PLIPMI_FLAG_DENSE_LAST_BLOCK | PLIPMI_FLAG_PACK_CAPTIONS | PLIPMI_FLAG_VALU_ATTENTION |
-                  PLIPMI_FLAG_TEXT_TOWER_F16))
+                  PLIPMI_FLAG_TEXT_TOWER_F16 | PLIPMI_FLAG_VISION_GELU | PLIPMI_FLAG_TEXT_GELU))
     return fail(PLIPMI_ERR_INVALID, "unknown bits in plipmi_config.flags (0x%x)", (unsigned)g.flags);
   if ((g.flags & PLIPMI_FLAG_TEXT_TOWER_F16) && g.compute_dtype != PLIPMI_BF16)
     return fail(PLIPMI_ERR_INVALID, "PLIPMI_FLAG_TEXT_TOWER_F16 is a mode of the bf16 engine (compute_dtype PLIPMI_BF16)");
@@ -70,6 +70,8 @@ inline void init_model(Model* m, const plipmi_config& g) {
   m->vis.dtype = m->dtype;
   m->txt.dtype = (g.flags & PLIPMI_FLAG_TEXT_TOWER_F16) ? PLIPMI_F16 : m->dtype;
   m->txt.lead_f16 = m->txt.dtype == PLIPMI_BF16 ? g.text_f16_layers : 0;
+  m->vis.gelu = (g.flags & PLIPMI_FLAG_VISION_GELU) != 0;
+  m->txt.gelu = (g.flags & PLIPMI_FLAG_TEXT_GELU) != 0;
 }
 
 // plipmi_clone_resolution's argument checks; *max_batch_out = the derived handle's batch (max_batch 0: the largest batch whose

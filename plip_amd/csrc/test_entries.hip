@@ -68,6 +68,26 @@ int plipmi_gemm_nt_ln_rows(int dtype, int mode, int variant, int M, int N, int K
   return gemm_nt_ln_entry(dtype, mode, variant, M, N, K, A, W, bias, stats, ns, eps, C, xb_out, st_out, m_dev, stream);
 }
 
+int plipmi_gemm_nt_gelu(int dtype, int ln, int variant, int M, int N, int K, const void* A, const void* W, const float* bias,
+                        const float* stats, int ns, float eps, void* C, void* stream) {
+  if (!valid_dtype(dtype)) return fail(PLIPMI_ERR_INVALID, "bad dtype");
+  if (ln != 0 && ln != 1) return fail(PLIPMI_ERR_INVALID, "ln must be 0 (gelu(A.W^T + bias)) or 1 (gelu(rstd * A.W^T + bias))");
+  if (ln && !half_code(dtype)) return fail(PLIPMI_ERR_INVALID, "LayerNorm-folded epilogues are 16-bit-engine forms");
+  if (M < 0 || N <= 0 || K <= 0 || !A || !W || !C || !bias) return fail(PLIPMI_ERR_INVALID, "bad shape / null pointer");
+  if (ln && (!stats || ns <= 0)) return fail(PLIPMI_ERR_INVALID, "ln = 1 needs the row statistics");
+  if (ln && ns % 2) return fail(PLIPMI_ERR_INVALID, "ln = 1 reads the statistics two slices at a time: ns = %d must be even (LayerNorm widths are multiples of 128)", ns);
+  if (ln && variant == -2) return fail(PLIPMI_ERR_INVALID, "ln = 1 at variant -2: the naive checker has no LayerNorm-folded form");
+  if (variant == -3 && !half_code(dtype)) return fail(PLIPMI_ERR_INVALID, "variant -3: the small-M kernel takes 16-bit operands");
+  GemmParams p = make_params(A, W, C, bias, M, N, K, K, K, N);
+  if (ln) { p.ln_stats = stats; p.ln_ns = ns; p.ln_inv_d = 1.0f / (float)(ns * kLnSlice); p.ln_eps = eps; }
+  const int epi = ln ? EPI_GELU_LN : EPI_BIAS_GELU;
+  const int rc = variant == -3 ? gemm_launch_skinny(dtype, epi, p, reinterpret_cast<hipStream_t>(stream), nullptr)
+                               : gemm_launch(dtype, epi, variant, p, reinterpret_cast<hipStream_t>(stream), nullptr);
+  if (rc != 0) return fail(PLIPMI_ERR_HIP, "gemm launch failed (gelu, ln %d, variant %d, M=%d N=%d K=%d): %s", ln, variant, M, N, K,
+                           hipGetErrorString((hipError_t)rc));
+  return PLIPMI_OK;
+}
+
 int plipmi_attention(int dtype, int impl, const void* qkv, void* out, int B, int S, int H, int causal,
                      const int64_t* key_mask, void* stream) {
   if (!valid_dtype(dtype) || !qkv || !out || B < 0 || S <= 0 || H <= 0)

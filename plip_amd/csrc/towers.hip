@@ -177,7 +177,7 @@ int run_layers(Forward& f, int n_layers, bool more_follow = false) {
     // t.st = the rows' statistics partials come from x's producer (embedding kernel, or the residual GEMM's epilogue); the
     // consuming GEMMs read the bf16 plane as their A operand, carry LayerNorm's gain, centring and bias in their weights and
     // apply rstd in their epilogues.  HF order (modeling_clip.py:370-381) is unchanged:
-    // x += out_proj(attn(LN1(x))); x += fc2(quick_gelu(fc1(LN2(x)))).
+    // x += out_proj(attn(LN1(x))); x += fc2(act(fc1(LN2(x)))), act = the tower's QuickGELU or GELU.
     const LnArgs use = f.ln_use(t.st);
     LnArgs emit; emit.xb_out = t.h; emit.st_out = t.st; emit.lo_io = t.lo;
     for (int l = 0; l < n_layers; ++l) {
@@ -185,7 +185,7 @@ int run_layers(Forward& f, int n_layers, bool more_follow = false) {
       RUN(enter_block(f, l));
       RUN(run_qkv_attention(f, w, use, tap_of(l)));
       RUN(run_gemm(f, EPI_RESID_SPLIT, t.att, w.wo, nullptr, w.bo, M, D, D, D, 0, "out_proj", &emit, md));
-      RUN(run_gemm(f, EPI_QGELU_LN, t.h, w.w1, t.mlp, w.b1, M, F, D, F, 0, "fc1", &use, md));
+      RUN(run_gemm(f, f.m.fc1_epi(true), t.h, w.w1, t.mlp, w.b1, M, F, D, F, 0, "fc1", &use, md));
       // a block whose successor runs on the other 16-bit operand type (the last f16 block of a mixed text tower) writes its
       // planes in the successor's format from fc2's epilogue -- no re-coding pass over the stream (the tiled kernels only:
       // the small-M kernel of the latency path keeps the separate pass, enter_block)
@@ -216,7 +216,7 @@ int run_layers(Forward& f, int n_layers, bool more_follow = false) {
     RUN(run_gemm(f, EPI_BIAS_RESID, t.att, w.wo, t.x, w.bo, M, D, D, D, 0, "out_proj"));
     { Scope sc(e, s, "layernorm", 0, (double)M * D * (4 + f.md.esz));
       HIP_TRY(launch_layernorm(t.x, D, w.ln2w, w.ln2b, t.h, f.cur, M, D, eps, s)); }
-    RUN(run_gemm(f, EPI_BIAS_QGELU, t.h, w.w1, t.mlp, w.b1, M, F, D, F, 0, "fc1"));
+    RUN(run_gemm(f, f.m.fc1_epi(false), t.h, w.w1, t.mlp, w.b1, M, F, D, F, 0, "fc1"));
     RUN(run_gemm(f, EPI_BIAS_RESID, t.mlp, w.w2, t.x, w.b2, M, D, F, D, 0, "fc2"));
     if (float* hs = hidden_of(l)) HIP_TRY(hipMemcpyAsync(hs, t.x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
   }
@@ -240,7 +240,7 @@ int run_last_block_pooled(Forward& f, const int64_t* ids, int eos_id) {
   LnArgs emit; emit.xb_out = t.hp; emit.st_out = t.stp;
   const LnArgs use = f.ln_use(t.stp);
   RUN(run_gemm(f, EPI_RESID_EMIT, t.attp, w.wo, t.xp, w.bo, B, D, D, D, 0, "~out_proj_pooled", &emit));
-  RUN(run_gemm(f, EPI_QGELU_LN, t.hp, w.w1, t.mlpp, w.b1, B, F, D, F, 0, "~fc1_pooled", &use));
+  RUN(run_gemm(f, f.m.fc1_epi(true), t.hp, w.w1, t.mlpp, w.b1, B, F, D, F, 0, "~fc1_pooled", &use));
   RUN(run_gemm(f, EPI_BIAS_RESID, t.mlpp, w.w2, t.xp, w.b2, B, D, F, D, 0, "~fc2_pooled"));
   return PLIPMI_OK;
 }

@@ -30,6 +30,14 @@ from .weights import synthetic_state_dict
 DEFAULT_TEXT_F16_LAYERS = 8
 
 
+def _activation_flags(cfg: PlipConfig) -> int:
+    """The plipmi_config.flags bits that say which MLP activation each tower runs: ``cfg.v_hidden_act`` / ``cfg.t_hidden_act`` ==
+    "gelu" -> PLIPMI_FLAG_VISION_GELU / PLIPMI_FLAG_TEXT_GELU, "quick_gelu" -> no bit (the engine's default kernels)."""
+    cfg.validate()      # any other name is refused, never run as QuickGELU
+    return ((_lib.FLAG_VISION_GELU if cfg.v_hidden_act == "gelu" else 0) |
+            (_lib.FLAG_TEXT_GELU if cfg.t_hidden_act == "gelu" else 0))
+
+
 class Engine(StreamsMixin, HeadsMixin, ResizeMixin, OutputsMixin):
     """One MI355X engine = packed weights + workspace for ``max_batch`` images/captions."""
 
@@ -50,6 +58,7 @@ class Engine(StreamsMixin, HeadsMixin, ResizeMixin, OutputsMixin):
         (plipmi_config.pass_batch: None = automatic -- 256 for ViT-B/32 --, 0 / negative = never split); same bits either way.
         ``latency_batch``: batches of at most that many samples run on the split-K small-M GEMMs (plipmi_set_latency_batch;
         faster up to batch 8, embeddings then differ from the big-batch path's by up to 6e-4 -- off by default).
+        The MLP activation of each tower (QuickGELU or the erf GELU) is the config's: ``cfg.v_hidden_act`` / ``cfg.t_hidden_act``.
         All of it is per-handle configuration (include/plipmi.h plipmi_config.flags): no environment variables.
         (``_config_struct_size``: ABI tests only -- announce a plipmi_config of that many bytes, as a caller compiled against
         an older, shorter header would.)"""
@@ -69,7 +78,7 @@ class Engine(StreamsMixin, HeadsMixin, ResizeMixin, OutputsMixin):
         self.dtype_name = {_lib.BF16: "bf16", _lib.F32: "f32", _lib.F16: "f16"}[self.dtype_code]
         self.flags = ((0 if ln_fold else _lib.FLAG_SEPARATE_LAYERNORM) | (0 if pooled_last_block else _lib.FLAG_DENSE_LAST_BLOCK) |
                       (_lib.FLAG_PACK_CAPTIONS if pack_captions else 0) | (0 if mfma_attention else _lib.FLAG_VALU_ATTENTION) |
-                      (_lib.FLAG_TEXT_TOWER_F16 if text_f16 else 0))
+                      (_lib.FLAG_TEXT_TOWER_F16 if text_f16 else 0) | _activation_flags(cfg))
         gb = 0 if graph_batch is None else (-1 if int(graph_batch) <= 0 else int(graph_batch))
         if text_f16_layers is None:
             text_f16_layers = min(DEFAULT_TEXT_F16_LAYERS, cfg.t_layers) if (self.dtype_code == _lib.BF16 and not text_f16) else 0

@@ -113,6 +113,25 @@ def gemm_nt_ln(mode: int, a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, 
         return out, xb, st
 
 
+def gemm_nt_gelu(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stats: Optional[torch.Tensor] = None, eps: float = 1e-5,
+                 variant: int = -1, out: Optional[torch.Tensor] = None, ln: Optional[bool] = None) -> torch.Tensor:
+    """Kernel-level entry (tests) for the exact-GELU epilogues (plipmi_gemm_nt_gelu): gelu(A @ W^T + bias) in a's dtype, or with
+    ``stats`` [M, ns, 2] the LayerNorm-folded form gelu(rstd * A @ W^T + bias) (16-bit).  ``ln`` overrides what ``stats`` implies."""
+    lib = _lib.load()
+    assert a.is_cuda and w.is_cuda and a.dtype == w.dtype and a.is_contiguous() and w.is_contiguous()
+    M, K = a.shape
+    N = w.shape[0]
+    if ln is None:
+        ln = stats is not None
+    if out is None:
+        out = torch.empty((M, N), dtype=a.dtype, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(lib.plipmi_gemm_nt_gelu(_code(a.dtype), int(ln), variant, M, N, K, _ptr(a), _ptr(w), _ptr(bias), _ptr(stats),
+                                           0 if stats is None else stats.shape[1], float(eps), _ptr(out), _stream_ptr(a.device)),
+                   "plipmi_gemm_nt_gelu")
+    return out
+
+
 def _pow2(k: torch.Tensor) -> torch.Tensor:
     """2^k as float64, built from the bit pattern (torch.pow / torch.ldexp are not exact on the GPU)"""
     return ((k.to(torch.int64) + 1023) << 52).view(torch.float64)

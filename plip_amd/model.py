@@ -86,20 +86,23 @@ class PlipModel:
 
     # ---- construction -----------------------------------------------------
     @classmethod
-    def from_state_dict(cls, state_dict, cfg: Optional[PlipConfig] = None, **kw) -> "PlipModel":
-        sd, cfg = W.normalize_state_dict(state_dict, cfg)
+    def from_state_dict(cls, state_dict, cfg: Optional[PlipConfig] = None, hidden_act=None, **kw) -> "PlipModel":
+        """``hidden_act``: "gelu" / "quick_gelu" / a ``(vision, text)`` pair, overriding the config's (weights.normalize_state_dict)."""
+        sd, cfg = W.normalize_state_dict(state_dict, cfg, hidden_act)
         return cls(cfg, sd, **kw)
 
     @classmethod
-    def from_pretrained(cls, path: str, arch: Optional[str] = None, **kw) -> "PlipModel":
+    def from_pretrained(cls, path: str, arch: Optional[str] = None, hidden_act=None, **kw) -> "PlipModel":
         """Local HF directory (what ``CLIPModel.from_pretrained`` takes, plip.py:26) or an
-        OpenAI-clip ``.pt`` state dict (factory.py:23-25).  No hub download: this box has no network."""
-        sd, cfg = W.load_checkpoint(path, arch)
+        OpenAI-clip ``.pt`` state dict (factory.py:23-25).  No hub download: this box has no network.
+        ``hidden_act``: the towers' MLP activation where the checkpoint cannot say it (an open_clip ``.pt``: "gelu") or to
+        override its ``config.json`` -- "gelu", "quick_gelu" or a ``(vision, text)`` pair (weights.load_checkpoint)."""
+        sd, cfg = W.load_checkpoint(path, arch, hidden_act=hidden_act)
         return cls(cfg, sd, **kw)
 
     @classmethod
-    def from_synthetic(cls, arch: str = "ViT-B/32", seed: int = 0, logit_scale=None, **kw) -> "PlipModel":
-        cfg = get_config(arch) if isinstance(arch, str) else arch
+    def from_synthetic(cls, arch: str = "ViT-B/32", seed: int = 0, logit_scale=None, hidden_act=None, **kw) -> "PlipModel":
+        cfg = (get_config(arch) if isinstance(arch, str) else arch).with_hidden_act(hidden_act)
         return cls(cfg, W.synthetic_state_dict(cfg, seed, logit_scale), **kw)
 
     # ---- nn.Module-ish no-ops the callers use ---------------------------------

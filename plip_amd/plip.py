@@ -55,7 +55,7 @@ class PLIP:
     def __init__(self, model_name: str = None, auth_token=None, *, model: Optional[PlipModel] = None,
                  tokenizer: Optional[Callable] = None, tokenizer_dir: Optional[str] = None, dtype: str = "bf16",
                  max_batch: int = 256, device: str = "cuda:0", pack_captions: bool = False, text_f16: bool = False,
-                 text_f16_layers: Optional[int] = None, ragged_resize: bool = False):
+                 text_f16_layers: Optional[int] = None, ragged_resize: bool = False, hidden_act=None):
         """``model_name``: local HF directory (what ``CLIPModel/CLIPProcessor.from_pretrained`` take, plip.py:26-27)
         or an OpenAI-clip ``.pt`` state dict.  The tokenizer comes from ``tokenizer`` (a callable), else from
         ``tokenizer_dir`` / the model directory when it holds ``vocab.json`` + ``merges.txt``; with neither,
@@ -68,7 +68,9 @@ class PLIP:
         explicitly -- ``PLIP(model=PlipModel.from_pretrained(path, **engine_options))``.  ``ragged_resize`` (extension): a batch of
         uint8 / PIL images whose sizes DIFFER is resized and cropped on the GPU too (``Engine.resize_crop_ragged``, Pillow-exact)
         instead of image by image in host Pillow; batches of one size and native tiles keep their routes, float inputs and images
-        shrunk more than 64 x keep the host path.  Off: every route is as before."""
+        shrunk more than 64 x keep the host path.  Off: every route is as before.  ``hidden_act``: the towers' MLP activation where
+        the checkpoint cannot say it -- an open_clip / LAION ``.pt`` state dict needs ``hidden_act="gelu"`` -- or to override an HF
+        directory's ``config.json``: "gelu", "quick_gelu" or a ``(vision, text)`` pair (``weights.load_checkpoint``)."""
         if not torch.cuda.is_available():
             raise RuntimeError("plip_amd.PLIP needs an MI355X (ROCm) GPU; there is no CPU path")
         self.device = device
@@ -84,7 +86,7 @@ class PLIP:
                 tokenizer = load_tokenizer(cand)
         if model is None:
             model = PlipModel.from_pretrained(model_name, device=device, dtype=dtype, max_batch=max_batch, text_f16=text_f16,
-                                              text_f16_layers=text_f16_layers)
+                                              text_f16_layers=text_f16_layers, hidden_act=hidden_act)
         self.model = model.to(self.device)
         if pack_captions:
             self.model.engine.set_text_packing(True)

@@ -145,7 +145,8 @@ class EmbedderFactory:
     """``EmbedderFactory().factory(args)`` with ``args.model_name`` in {"plip", "clip"} and ``args.backbone`` = a local
     checkpoint (OpenAI-clip ``.pt`` state dict, as factory.py:21-25 loads, or an HF directory / .safetensors).  The
     architecture comes from ``$PC_CLIP_ARCH`` (factory.py:21), default ViT-B/32.  Optional ``args.dtype`` ("bf16" |
-    "fp32"), ``args.max_batch`` and ``args.tokenizer_dir`` are extensions."""
+    "fp32"), ``args.max_batch``, ``args.tokenizer_dir`` and ``args.hidden_act`` ("gelu" for an open_clip / LAION state dict, which
+    cannot say it itself; ``weights.load_checkpoint``) are extensions."""
 
     def factory(self, args) -> CLIPEmbedder:
         name = args.model_name
@@ -157,7 +158,8 @@ class EmbedderFactory:
                     f"model_name={name!r} needs args.backbone to be a local checkpoint (got {path!r}); "
                     "this engine never downloads weights")
             model = PlipModel.from_pretrained(path, arch=arch, dtype=getattr(args, "dtype", "bf16"),
-                                              max_batch=int(getattr(args, "max_batch", 256)))
+                                              max_batch=int(getattr(args, "max_batch", 256)),
+                                              hidden_act=getattr(args, "hidden_act", None))
             tok = None
             tok_dir = getattr(args, "tokenizer_dir", None) or (path if os.path.isdir(path) else None)
             if tok_dir and os.path.exists(os.path.join(tok_dir, "vocab.json")):

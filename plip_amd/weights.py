@@ -329,8 +329,12 @@ def to_openai_state_dict(sd: Mapping[str, np.ndarray], cfg: PlipConfig) -> State
     return out
 
 
-def normalize_state_dict(sd: Mapping[str, object], cfg: PlipConfig | None = None):
-    """Return ``(hf_format_numpy_state_dict, cfg)`` for either checkpoint flavour."""
+def normalize_state_dict(sd: Mapping[str, object], cfg: PlipConfig | None = None, hidden_act=None):
+    """Return ``(hf_format_numpy_state_dict, cfg)`` for either checkpoint flavour.
+
+    ``hidden_act``: "gelu", "quick_gelu" or a ``(vision, text)`` pair -- the towers' MLP activation, overriding the config's.
+    A state dict carries no activation: for an OpenAI-format one (open_clip ``.pt`` files have the same keys as OpenAI's but come
+    from models built without ``quick_gelu``) this argument is the only way to say it."""
     if is_openai_state_dict(sd):
         if cfg is None:
             cfg = config_from_openai_state_dict(sd)
@@ -340,6 +344,7 @@ def normalize_state_dict(sd: Mapping[str, object], cfg: PlipConfig | None = None
                if not k.endswith("position_ids")}  # non-persistent buffer in old HF checkpoints
         if cfg is None:
             cfg = get_config("ViT-B/32")
+    cfg = cfg.with_hidden_act(hidden_act)
     out["logit_scale"] = np.float32(np.asarray(out["logit_scale"], dtype=np.float32).reshape(-1)[0])
     check_state_dict(out, cfg)
     return out, cfg
@@ -357,14 +362,19 @@ def check_state_dict(sd: Mapping[str, np.ndarray], cfg: PlipConfig) -> None:
             raise ValueError(f"{k}: shape {tuple(np.shape(sd[k]))}, expected {tuple(shp)}")
 
 
-def load_checkpoint(path: str, arch: str | None = None, trust_pickle: bool = False):
+def load_checkpoint(path: str, arch: str | None = None, trust_pickle: bool = False, hidden_act=None):
     """Load real PLIP weights from disk: an HF directory (``config.json`` +
     ``model.safetensors`` / ``pytorch_model.bin``, what plip.py:26 pulls from the
     hub) or an OpenAI-clip ``.pt`` state dict (factory.py:23-25).
 
     ``.pt`` / ``.bin`` files are read with ``weights_only=True`` (tensors only: a plain state dict needs nothing
     more).  Whole-model or TorchScript pickles execute code while loading; they are refused unless
-    ``trust_pickle=True`` (or ``PLIPMI_TRUST_PICKLE=1``) says the file comes from a trusted source."""
+    ``trust_pickle=True`` (or ``PLIPMI_TRUST_PICKLE=1``) says the file comes from a trusted source.
+
+    The towers' MLP activation comes from ``config.json`` (``vision_config.hidden_act`` / ``text_config.hidden_act``; absent =
+    "quick_gelu", HF's default).  ``hidden_act`` = "gelu", "quick_gelu" or a ``(vision, text)`` pair overrides it -- and is the only
+    way to say it for a ``.pt`` state dict: an open_clip / LAION checkpoint needs ``hidden_act="gelu"`` unless its model was built
+    with ``quick_gelu``."""
     import json
 
     import torch
@@ -372,9 +382,13 @@ def load_checkpoint(path: str, arch: str | None = None, trust_pickle: bool = Fal
     cfg = get_config(arch) if arch else None
     if os.path.isdir(path):
         cj = os.path.join(path, "config.json")
-        if cfg is None and os.path.exists(cj):
+        if os.path.exists(cj):
             with open(cj) as f:
-                cfg = from_hf_config(json.load(f))
+                hf = json.load(f)
+            if cfg is None:
+                cfg = from_hf_config(hf)
+            else:   # an explicit ``arch`` names the shapes; the activation is still the checkpoint's own (absent: HF's default)
+                cfg = cfg.with_hidden_act(tuple((hf.get(k) or {}).get("hidden_act") or "quick_gelu" for k in ("vision_config", "text_config")))
         st = os.path.join(path, "model.safetensors")
         if os.path.exists(st):
             from safetensors.numpy import load_file
@@ -414,4 +428,4 @@ def load_checkpoint(path: str, arch: str | None = None, trust_pickle: bool = Fal
             sd = sd.state_dict()
         if isinstance(sd, dict) and "state_dict" in sd and "logit_scale" not in sd:
             sd = sd["state_dict"]
-    return normalize_state_dict(sd, cfg)
+    return normalize_state_dict(sd, cfg, hidden_act)
