@@ -106,20 +106,24 @@ typedef struct plipmi_engine* plipmi_handle;
 /* Architecture = the numbers in HF CLIPConfig (configuration_clip.py:47-64,97-109).
  * `struct_size` = sizeof(plipmi_config) AS THE CALLER COMPILED IT: plipmi_create reads that many bytes and takes every later
  * member as 0 (= its default), so members appended in later versions do not turn into garbage for older callers; a size
- * smaller than the 0.4.0 struct (through `max_batch`) or larger than the library's own is rejected. */
+ * smaller than the 0.4.0 struct (through `max_batch`) or larger than the library's own is rejected.
+ * Attention head size, per tower: head_dim = width / heads.  64 -- every OpenAI CLIP / PLIP variant -- runs the kernels tuned for it
+ * (and only such a text tower takes the fused q/k/v + attention kernel and caption packing).  Any other multiple of 8 from 72 to 128
+ * (vision; text: to 120) runs the padded-head attention kernels: open_clip's ViT-H/14 (16 heads of 80) and ViT-g/14 (16 of 88) vision
+ * towers.  Everything else is PLIPMI_ERR_INVALID from plipmi_create, with a message that names head_dim. */
 typedef struct plipmi_config {
   int32_t struct_size;     /* sizeof(plipmi_config) */
   int32_t image_size;      /* 224 */
   int32_t patch_size;      /* 32  */
   int32_t v_width;         /* 768 */
   int32_t v_layers;        /* 12  */
-  int32_t v_heads;         /* 12  (head_dim must be 64) */
+  int32_t v_heads;         /* 12  (head_dim = v_width / v_heads: 64, or another multiple of 8 up to 128 -- see below) */
   int32_t v_mlp;           /* 3072 */
   int32_t vocab_size;      /* 49408 */
   int32_t context_length;  /* 77 */
   int32_t t_width;         /* 512 */
   int32_t t_layers;        /* 12 */
-  int32_t t_heads;         /* 8 */
+  int32_t t_heads;         /* 8   (head_dim = t_width / t_heads: 64, or another multiple of 8 up to 120) */
   int32_t t_mlp;           /* 2048 */
   int32_t projection_dim;  /* 512 */
   float   layer_norm_eps;  /* 1e-5 */
@@ -272,7 +276,8 @@ int plipmi_set_latency_batch(plipmi_handle h, int max_batch);
  * row offsets and the live-row count are derived from `ids` ON THE DEVICE (no host synchronisation; the path stays
  * graph-capturable), the GEMMs size their grids for the padded worst case and retire dead tiles at once, attention takes
  * per-caption lengths.  text_embeds are BIT-IDENTICAL to the padded computation.  A caption of L tokens then costs L/77 of
- * a padded one.  The default (off) executes every padded position, which is what the bench's headline line measures. */
+ * a padded one.  The default (off) executes every padded position, which is what the bench's headline line measures.
+ * A text tower whose head_dim is not 64 has no packed form: PLIPMI_ERR_INVALID (here and for PLIPMI_FLAG_PACK_CAPTIONS). */
 int plipmi_set_text_packing(plipmi_handle h, int on);
 
 /* Per-token tower outputs -- what HF CLIPModel.vision_model / .text_model return with output_hidden_states /

@@ -112,6 +112,10 @@ TEST_SYMBOLS = {
     "plipmi_gemm_nt_ln_rows": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "plipmi_attention_packed": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "plipmi_gemm_nt_gelu": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp]),
+    "plipmi_attention_hd": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "plipmi_attention_probs_hd": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "plipmi_attention_pooled_rows_hd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "plipmi_attention_rollout_step_hd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 # every symbol include/plipmi.h declares (the product interface): (restype, argtypes)
 SYMBOLS = {

@@ -22,7 +22,9 @@ SOURCES = ["engine.hip", "towers.hip", "heads.hip", "test_entries.hip", "gemm.hi
            "tower_kernels.hip", "attention.hip", "attention_mfma.hip", "qkv_attention.hip", "attention_probs.hip", "probe.hip", "resize_ragged.hip", "attention_summary.hip", "head_kernels.hip", "setup_kernels.hip",
            # the exact-GELU epilogues: units of their own, behind everything that existed (the other units' code objects and their
            # places in the link order are those of a build without them)
-           "gemm_gelu_f32.hip", "gemm_gelu_bf16.hip", "gemm_gelu_f16.hip", "gemm_skinny_gelu.hip"]
+           "gemm_gelu_f32.hip", "gemm_gelu_bf16.hip", "gemm_gelu_f16.hip", "gemm_skinny_gelu.hip",
+           # attention at head sizes other than 64, likewise behind everything that existed
+           "attention_valu_hd.hip", "attention_mfma_hd.hip", "attention_probs_hd.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-Wno-unused-value"]
 
@@ -47,7 +49,7 @@ def source_digest() -> str:
     """sha256 (first 16 hex digits) over every kernel source and header of libplipmi.so: the identity of the code a
     measurement was taken on.  bench.py stamps its line with it and refuses profiles/pmc_traffic.json when that file
     was collected on different sources."""
-    paths = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))]
+    paths = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc", ".hip"))]
     for hdr in ("plipmi.h", "plipmi_test.h"):
         paths.append(os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", hdr))
     h = hashlib.sha256()
@@ -69,7 +71,7 @@ def _compile(hipcc: str, src: str, obj: str) -> str:
 def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = _hipcc()
     os.makedirs(BUILD, exist_ok=True)
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]   # .inc: kernel bodies included as text
     for hdr in ("plipmi.h", "plipmi_test.h"):
         headers.append(os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", hdr))
     hdr_digest = _digest(headers)

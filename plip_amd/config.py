@@ -16,6 +16,9 @@ from dataclasses import dataclass
 
 # the MLP activations the engine has kernels for (HF ``hidden_act`` names)
 HIDDEN_ACTS = ("quick_gelu", "gelu")
+# attention head sizes (width // heads) the engine has kernels for, per tower: 64 -- every OpenAI CLIP / PLIP variant --, or another
+# multiple of 8 up to the largest listed here (csrc/handle_host.h validate_config: ViT-H/14's vision heads are 80 wide, ViT-g/14's 88)
+MAX_HEAD_DIM = {"v": 128, "t": 120}
 
 
 @dataclass(frozen=True)
@@ -68,12 +71,19 @@ class PlipConfig:
     def head_dim(self) -> int:
         return self.v_width // self.v_heads
 
+    @property
+    def t_head_dim(self) -> int:
+        return self.t_width // self.t_heads
+
     def validate(self) -> None:
-        if self.v_width % self.v_heads or self.t_width % self.t_heads:
-            raise ValueError("width must be a multiple of heads")
-        if self.v_width // self.v_heads != 64 or self.t_width // self.t_heads != 64:
-            raise ValueError("the MI355X kernels are built for head_dim == 64 "
-                             "(true for every published CLIP/PLIP variant)")
+        for tower in ("v", "t"):
+            width, heads = getattr(self, tower + "_width"), getattr(self, tower + "_heads")
+            if heads <= 0 or width % heads:
+                raise ValueError(f"{tower}_width = {width} must be a multiple of {tower}_heads = {heads}")
+            head = width // heads
+            if head % 8 or not 64 <= head <= MAX_HEAD_DIM[tower]:
+                raise ValueError(f"head_dim = {tower}_width // {tower}_heads = {head}: the MI355X attention kernels take a multiple "
+                                 f"of 8 from 64 to {MAX_HEAD_DIM[tower]} for this tower")
         if self.image_size % self.patch_size:
             raise ValueError("image_size must be a multiple of patch_size")
         for name in ("v_width", "v_mlp", "t_width", "t_mlp"):
@@ -141,6 +151,13 @@ PRESETS = {
     "ViT-L/14@336px": PlipConfig(image_size=336, patch_size=14, v_width=1024, v_layers=24,
                                  v_heads=16, v_mlp=4096, t_width=768, t_heads=12, t_mlp=3072,
                                  projection_dim=768),
+    # open_clip / LAION-trained towers whose vision heads are not 64 wide (80 and 88); the text tower of both is 1024 wide with 16
+    # heads of 64.  Like every preset these name SHAPES: the published checkpoints use the erf GELU in both towers, which comes from
+    # the checkpoint's config.json or from ``hidden_act="gelu"`` (``with_hidden_act``), as for any other open_clip checkpoint.
+    "ViT-H/14": PlipConfig(patch_size=14, v_width=1280, v_layers=32, v_heads=16, v_mlp=5120, t_width=1024, t_layers=24, t_heads=16,
+                           t_mlp=4096, projection_dim=1024),
+    "ViT-g/14": PlipConfig(patch_size=14, v_width=1408, v_layers=40, v_heads=16, v_mlp=6144, t_width=1024, t_layers=24, t_heads=16,
+                           t_mlp=4096, projection_dim=1024),
     # small shapes for CPU-side tests and golden fixtures (same code paths,
     # every GEMM/LN/attention constraint of the kernels still holds)
     "tiny": PlipConfig(image_size=64, patch_size=16, v_width=128, v_layers=2, v_heads=2,

@@ -4,7 +4,7 @@
 //
 // Data layout in HBM
 //   weights    one slab per MODEL, shared by a handle and its clones (handle.h Model): per layer Wqkv [3D,D] (q rows pre-scaled by
-//              1/8 = 64^-1/2, exact), Wo [D,D], W1 [F,D], W2 [D,F] in the tower's operand type, K contiguous (= the HF [out,in]
+//              head^-1/2: 1/8 at head 64, exact), Wo [D,D], W1 [F,D], W2 [D,F] in the tower's operand type, K contiguous (= the HF [out,in]
 //              layout, so no transposes) -- on a LayerNorm-folded engine Wqkv / W1 carry the LayerNorm gain and centring;
 //              biases / LayerNorm / embeddings fp32; projection matrices fp32 as [P,D] and transposed [D,P].
 //   workspace  one slab per HANDLE, sized for its max_batch (handle.h Tower; M = B * tokens): per tower x fp32 [M,D] (embedding
@@ -12,6 +12,7 @@
 //              as two planes -- h [M,D] operand type + lo 8-bit remainder -- with the rows' LayerNorm statistics st [M,D/64,2];
 //              the pooled last block's [B,*] rows; the patch rows; the staging buffers of the captured small-batch graphs.
 //              The two towers have separate workspaces so they can run on two streams.
+#include <math.h>
 #include <stdio.h>
 #include <time.h>
 
@@ -59,7 +60,9 @@ namespace {
 
 int pack_tower(const Model& m, const TowerModel& t, const plipmi_layer_weights* src, hipStream_t s) {
   const int D = t.D, F = t.F;
-  const float qscale = 0.125f;  // head_dim 64 -> 64^-0.5, a power of two: folding it into Wq/bq is exact
+  // head_dim^-0.5 folded into Wq / bq: computed in double and rounded once to fp32.  Head 64: exactly 0.125, a power of two, so
+  // the fold is exact; any other head (72 .. 128) rounds the scaled weights once more, in fp32, before their operand rounding
+  const float qscale = (float)(1.0 / sqrt((double)t.head()));
   for (int l = 0; l < t.L; ++l) {
     const int dt = t.layer_dtype(l);
     const plipmi_layer_weights& w = src[l];
@@ -248,6 +251,9 @@ int plipmi_set_text_packing(plipmi_handle h, int on) {
   if (!h) return fail(PLIPMI_ERR_INVALID, "null handle");
   if (on && !h->model->pooled_last)
     return fail(PLIPMI_ERR_INVALID, "caption packing needs a 16-bit engine's pooled last block (compute_dtype bf16 / f16, LayerNorm folding on, last block not dense)");
+  if (on && h->model->txt.head() != 64)
+    return fail(PLIPMI_ERR_INVALID, "caption packing needs a text tower with head_dim 64: packed rows are a form of the head-64 short-sequence "
+                "attention kernel (this tower: t_width=%d/%d heads = %d)", h->model->txt.D, h->model->txt.H, h->model->txt.head());
   if ((on != 0) != h->text_pack) h->graphs.clear();   // captured text forwards hold the other form's launches
   h->text_pack = on != 0;
   return PLIPMI_OK;

@@ -174,6 +174,7 @@ struct LayerW {
 };
 struct TowerModel {
   int D = 0, F = 0, L = 0, H = 0;
+  int head() const { return D / H; }   // columns of one attention head: 64, or 72 .. 128 in steps of 8 (validate_config)
   int dtype = 0;   // operand type of this tower's GEMMs / attention (the engine's, or f16 for the text tower under PLIPMI_FLAG_TEXT_TOWER_F16)
   // plipmi_config.text_f16_layers: the first lead_f16 blocks of a bf16 text tower run on IEEE-half operands (the blocks where
   // bf16's operand rounding costs the embeddings most -- DESIGN.md section 2.1), the rest on the tower's type.

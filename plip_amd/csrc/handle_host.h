@@ -42,9 +42,18 @@ inline int validate_config(const plipmi_config* cfg, plipmi_config* g_out) {
     return fail(PLIPMI_ERR_INVALID, "PLIPMI_FLAG_TEXT_TOWER_F16 is a mode of the bf16 engine (compute_dtype PLIPMI_BF16)");
   if (g.text_f16_layers < 0 || g.text_f16_layers > g.t_layers || (g.text_f16_layers > 0 && g.compute_dtype != PLIPMI_BF16))
     return fail(PLIPMI_ERR_INVALID, "text_f16_layers = %d: 0 .. t_layers leading text blocks, bf16 engine only", g.text_f16_layers);
-  if (g.v_heads <= 0 || g.t_heads <= 0 || g.v_width != g.v_heads * 64 || g.t_width != g.t_heads * 64)
-    return fail(PLIPMI_ERR_INVALID, "head_dim must be 64 (v_width=%d/%d heads, t_width=%d/%d heads)", g.v_width,
-                g.v_heads, g.t_width, g.t_heads);
+  // head_dim = width / heads, per tower: 64 (the kernels every OpenAI CLIP / PLIP variant runs), or another multiple of 8 up to 128
+  // (the padded-head attention kernels: ViT-H/14's vision heads are 80 wide, ViT-g/14's 88) -- a text tower up to 120: no published
+  // CLIP has a wider text head
+  auto head_ok = [](int width, int heads, int max_head) {
+    return heads > 0 && width > 0 && width % heads == 0 && width / heads % 8 == 0 && width / heads >= 64 && width / heads <= max_head;
+  };
+  if (!head_ok(g.v_width, g.v_heads, 128) || !head_ok(g.t_width, g.t_heads, 120))
+    return fail(PLIPMI_ERR_INVALID, "head_dim = width / heads must be a multiple of 8, 64 .. 128 (vision) / 64 .. 120 (text) "
+                "(v_width=%d/%d heads, t_width=%d/%d heads)", g.v_width, g.v_heads, g.t_width, g.t_heads);
+  if ((g.flags & PLIPMI_FLAG_PACK_CAPTIONS) && g.t_width != g.t_heads * 64)
+    return fail(PLIPMI_ERR_INVALID, "PLIPMI_FLAG_PACK_CAPTIONS needs a text tower with head_dim 64: packed rows are a form of the head-64 "
+                "short-sequence attention kernel (t_width=%d/%d heads)", g.t_width, g.t_heads);
   if (g.patch_size <= 0 || g.image_size % g.patch_size) return fail(PLIPMI_ERR_INVALID, "image_size %% patch_size != 0");
   if (g.v_width % 128 || g.v_mlp % 128 || g.t_width % 128 || g.t_mlp % 128)
     return fail(PLIPMI_ERR_INVALID, "widths and MLP sizes must be multiples of 128 (GEMM tile)");

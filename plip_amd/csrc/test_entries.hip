@@ -90,10 +90,22 @@ int plipmi_gemm_nt_gelu(int dtype, int ln, int variant, int M, int N, int K, con
 
 int plipmi_attention(int dtype, int impl, const void* qkv, void* out, int B, int S, int H, int causal,
                      const int64_t* key_mask, void* stream) {
+  return plipmi_attention_hd(dtype, impl, qkv, out, B, S, H, 64, causal, key_mask, stream);
+}
+// what every *_hd entry refuses in front of its launcher: a head size no attention kernel is built for
+static int check_head_dim(int head_dim) {
+  if (!attention_head_ok(head_dim))
+    return fail(PLIPMI_ERR_INVALID, "head_dim = %d: the attention kernels take 64, or 72 .. 128 in steps of 8", head_dim);
+  return PLIPMI_OK;
+}
+int plipmi_attention_hd(int dtype, int impl, const void* qkv, void* out, int B, int S, int H, int head_dim, int causal,
+                        const int64_t* key_mask, void* stream) {
   if (!valid_dtype(dtype) || !qkv || !out || B < 0 || S <= 0 || H <= 0)
     return fail(PLIPMI_ERR_INVALID, "bad argument");
-  hipError_t e = launch_attention(qkv, out, dtype, B, S, H, causal, key_mask, impl, reinterpret_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(PLIPMI_ERR_HIP, "attention launch (impl %d, S=%d) failed: %s", impl, S, hipGetErrorString(e));
+  RUN(check_head_dim(head_dim));
+  hipError_t e = launch_attention(qkv, out, dtype, B, S, H, head_dim, causal, key_mask, impl, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess)
+    return fail(PLIPMI_ERR_HIP, "attention launch (impl %d, S=%d, head_dim=%d) failed: %s", impl, S, head_dim, hipGetErrorString(e));
   return PLIPMI_OK;
 }
 
@@ -101,7 +113,7 @@ int plipmi_attention_packed(int dtype, int impl, const void* qkv, void* out, int
                             const int32_t* cu, void* stream) {
   if (!half_code(dtype) || !qkv || !out || !cu || B < 0 || S <= 0 || H <= 0) return fail(PLIPMI_ERR_INVALID, "bad argument (16-bit dtype, qkv, out, cu non-null)");
   if (impl != 1 || S > 128) return fail(PLIPMI_ERR_INVALID, "packed rows are a form of the short-sequence MFMA kernel: impl 1, S <= 128 (got impl %d, S=%d)", impl, S);
-  hipError_t e = launch_attention(qkv, out, dtype, B, S, H, causal, key_mask, impl, reinterpret_cast<hipStream_t>(stream), cu);
+  hipError_t e = launch_attention(qkv, out, dtype, B, S, H, 64, causal, key_mask, impl, reinterpret_cast<hipStream_t>(stream), cu);
   if (e != hipSuccess) return fail(PLIPMI_ERR_HIP, "packed attention launch (S=%d) failed: %s", S, hipGetErrorString(e));
   return PLIPMI_OK;
 }
@@ -180,26 +192,41 @@ int plipmi_resize_ragged_tables(int in_size, int out_size, int first, int count,
 
 int plipmi_attention_probs(int dtype, const void* qkv, float* probs, int B, int S, int H, int causal, const int64_t* key_mask,
                            void* stream) {
+  return plipmi_attention_probs_hd(dtype, qkv, probs, B, S, H, 64, causal, key_mask, stream);
+}
+int plipmi_attention_probs_hd(int dtype, const void* qkv, float* probs, int B, int S, int H, int head_dim, int causal,
+                              const int64_t* key_mask, void* stream) {
   if (!valid_dtype(dtype) || !qkv || !probs || B < 0 || S <= 0 || S > 1024 || H <= 0)
     return fail(PLIPMI_ERR_INVALID, "bad argument (qkv, probs non-null, 1 <= S <= 1024, H >= 1)");
-  const hipError_t e = launch_attention_probs(qkv, probs, dtype, B, S, H, causal, key_mask, reinterpret_cast<hipStream_t>(stream));
+  RUN(check_head_dim(head_dim));
+  const hipError_t e = launch_attention_probs(qkv, probs, dtype, B, S, H, head_dim, causal, key_mask, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(PLIPMI_ERR_HIP, "attention probabilities launch (S=%d) failed: %s", S, hipGetErrorString(e));
   return PLIPMI_OK;
 }
 int plipmi_attention_pooled_rows(int dtype, const void* qkv, const int32_t* rows, float* out, int B, int S, int H, int causal,
                                  const int64_t* key_mask, void* stream) {
+  return plipmi_attention_pooled_rows_hd(dtype, qkv, rows, out, B, S, H, 64, causal, key_mask, stream);
+}
+int plipmi_attention_pooled_rows_hd(int dtype, const void* qkv, const int32_t* rows, float* out, int B, int S, int H, int head_dim,
+                                    int causal, const int64_t* key_mask, void* stream) {
   if (!valid_dtype(dtype) || !qkv || !rows || !out || B < 0 || B > 65535 || S <= 0 || S > 1024 || H <= 0)
     return fail(PLIPMI_ERR_INVALID, "bad argument (qkv, rows, out non-null, B <= 65535, 1 <= S <= 1024, H >= 1)");
-  const hipError_t e = launch_attention_pooled_rows(qkv, rows, out, dtype, B, S, H, causal, key_mask, reinterpret_cast<hipStream_t>(stream));
+  RUN(check_head_dim(head_dim));
+  const hipError_t e = launch_attention_pooled_rows(qkv, rows, out, dtype, B, S, H, head_dim, causal, key_mask, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(PLIPMI_ERR_HIP, "pooled attention rows launch (S=%d) failed: %s", S, hipGetErrorString(e));
   return PLIPMI_OK;
 }
 int plipmi_attention_rollout_step(int dtype, const void* qkv, const float* R_in, float* R_out, int B, int S, int H, int causal,
                                   const int64_t* key_mask, void* stream) {
+  return plipmi_attention_rollout_step_hd(dtype, qkv, R_in, R_out, B, S, H, 64, causal, key_mask, stream);
+}
+int plipmi_attention_rollout_step_hd(int dtype, const void* qkv, const float* R_in, float* R_out, int B, int S, int H, int head_dim,
+                                     int causal, const int64_t* key_mask, void* stream) {
   if (!valid_dtype(dtype) || !qkv || !R_out || B < 0 || B > 65535 || S <= 0 || S > 1024 || H <= 0)
     return fail(PLIPMI_ERR_INVALID, "bad argument (qkv, R_out non-null, B <= 65535, 1 <= S <= 1024, H >= 1)");
   if (R_in == R_out) return fail(PLIPMI_ERR_INVALID, "R_out must not be R_in: every tile of a step reads all of R_in");
-  const hipError_t e = launch_attention_rollout_step(qkv, R_in, R_out, dtype, B, S, H, causal, key_mask, reinterpret_cast<hipStream_t>(stream));
+  RUN(check_head_dim(head_dim));
+  const hipError_t e = launch_attention_rollout_step(qkv, R_in, R_out, dtype, B, S, H, head_dim, causal, key_mask, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(PLIPMI_ERR_HIP, "attention rollout step launch (S=%d) failed: %s", S, hipGetErrorString(e));
   return PLIPMI_OK;
 }

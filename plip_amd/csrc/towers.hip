@@ -121,28 +121,28 @@ int enter_block(Forward& f, int l) {
 // first, as the call's Taps ask (unpacked rows only)
 int run_attention(Forward& f, int tap) {
   const Tower& t = f.t;
-  const int H = f.m.H, S = t.S, B = f.B;
+  const int H = f.m.H, S = t.S, B = f.B, hd = f.m.head();
   const Taps* taps = tap >= 0 ? f.taps : nullptr;
   if (taps && taps->probs) {
-    Scope sc(f.e, f.s, "attention_probs", 2.0 * B * H * (double)S * S * 64, (double)B * H * S * S * 4);
-    HIP_TRY(launch_attention_probs(t.qkv, taps->probs + (size_t)tap * B * H * S * S, f.cur, B, S, H, f.causal, f.key_mask, f.s));
+    Scope sc(f.e, f.s, "attention_probs", 2.0 * B * H * (double)S * S * hd, (double)B * H * S * S * 4);
+    HIP_TRY(launch_attention_probs(t.qkv, taps->probs + (size_t)tap * B * H * S * S, f.cur, B, S, H, hd, f.causal, f.key_mask, f.s));
   }
   // (with a rollout in the same call, its step stores the pooled rows on its way: the tile that holds them forms them anyway)
   if (taps && taps->pooled_rows && !taps->rollout[0]) {
-    Scope sc(f.e, f.s, "attention_pooled_rows", 2.0 * B * H * (double)S * 64, (double)B * H * S * (4 + 2.0 * 64 * f.md.esz));
-    HIP_TRY(launch_attention_pooled_rows(t.qkv, taps->row_idx, taps->pooled_rows + (size_t)tap * B * H * S, f.cur, B, S, H, f.causal,
+    Scope sc(f.e, f.s, "attention_pooled_rows", 2.0 * B * H * (double)S * hd, (double)B * H * S * (4 + 2.0 * hd * f.md.esz));
+    HIP_TRY(launch_attention_pooled_rows(t.qkv, taps->row_idx, taps->pooled_rows + (size_t)tap * B * H * S, f.cur, B, S, H, hd, f.causal,
                                          f.key_mask, f.s));
   }
   if (taps && taps->rollout[0]) {
-    Scope sc(f.e, f.s, "attention_rollout_step", 2.0 * B * H * (double)S * S * 64 + 2.0 * B * (double)S * S * S,
-             (double)B * S * (2.0 * H * 64 * f.md.esz + 8.0 * S));
+    Scope sc(f.e, f.s, "attention_rollout_step", 2.0 * B * H * (double)S * S * hd + 2.0 * B * (double)S * S * S,
+             (double)B * S * (2.0 * H * hd * f.md.esz + 8.0 * S));
     HIP_TRY(launch_attention_rollout_step(t.qkv, tap == 0 ? nullptr : taps->rollout[(tap - 1) & 1], taps->rollout[tap & 1], f.cur, B, S, H,
-                                          f.causal, f.key_mask, f.s, taps->row_idx,
+                                          hd, f.causal, f.key_mask, f.s, taps->row_idx,
                                           taps->pooled_rows ? taps->pooled_rows + (size_t)tap * B * H * S : nullptr));
   }
   const int impl = f.attn_impl();
-  Scope sc(f.e, f.s, impl ? "attention_mfma" : "attention_valu", 4.0 * B * H * (double)S * S * 64, (double)f.M() * 4 * f.m.D * f.md.esz);
-  HIP_TRY(launch_attention(t.qkv, t.att, f.cur, B, S, H, f.causal, f.key_mask, impl, f.s, f.cu()));
+  Scope sc(f.e, f.s, impl ? "attention_mfma" : "attention_valu", 4.0 * B * H * (double)S * S * hd, (double)f.M() * 4 * f.m.D * f.md.esz);
+  HIP_TRY(launch_attention(t.qkv, t.att, f.cur, B, S, H, hd, f.causal, f.key_mask, impl, f.s, f.cu()));
   return PLIPMI_OK;
 }
 
@@ -154,7 +154,7 @@ int run_qkv_attention(Forward& f, const LayerW& w, const LnArgs& use, int tap = 
   const int M = f.M(), D = f.m.D, H = f.m.H, B = f.B;
   if (tap < 0 && g_fuse_qkv_attention && f.attn_impl() == 1 && !f.packed && !f.small && qkv_attention_supports(f.cur, B, t.S, H, D) &&
       (g_fuse_qkv_attention == 2 || qkv_attention_pays(B, H, gemm_num_cus()))) {
-    Scope sc(f.e, f.s, "qkv_attention", 2.0 * M * 3.0 * D * (double)D + 4.0 * B * H * (double)t.S * t.S * 64, ((double)M * D * 2 + 3.0 * D * D) * f.md.esz);
+    Scope sc(f.e, f.s, "qkv_attention", 2.0 * M * 3.0 * D * (double)D + 4.0 * B * H * (double)t.S * t.S * f.m.head(), ((double)M * D * 2 + 3.0 * D * D) * f.md.esz);
     HIP_TRY(launch_qkv_attention(f.cur, t.h, w.wqkv, w.bqkv, use.stats, use.inv_d, use.eps, t.att, B, t.S, H, f.causal, f.key_mask, f.s));
     return PLIPMI_OK;
   }

@@ -51,15 +51,23 @@ def gemm_nt_ld(a: torch.Tensor, w: torch.Tensor, K: int, bias: Optional[torch.Te
 
 
 def attention(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool = False, key_mask: Optional[torch.Tensor] = None,
-              impl: int = 0) -> torch.Tensor:
-    """Kernel-level entry (tests): qkv [B*S, 3*H*64] (scale folded into q) -> [B*S, H*64]."""
+              impl: int = 0, head_dim: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Kernel-level entry (tests): qkv [B*S, 3*H*64] (scale folded into q) -> [B*S, H*64].  With ``head_dim`` the entry that carries
+    the head size (``plipmi_attention_hd``): qkv [B*S, 3*H*head_dim] -> [B*S, H*head_dim], into ``out`` if the caller brings one."""
     lib = _lib.load()
-    assert qkv.is_cuda and qkv.is_contiguous() and qkv.shape == (B * S, 3 * H * 64)
+    hd = 64 if head_dim is None else int(head_dim)
+    assert qkv.is_cuda and qkv.is_contiguous() and qkv.shape == (B * S, 3 * H * hd)
     code = _code(qkv.dtype)
-    out = torch.empty((B * S, H * 64), dtype=qkv.dtype, device=qkv.device)
+    if out is None:
+        out = torch.empty((B * S, H * hd), dtype=qkv.dtype, device=qkv.device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == qkv.dtype and out.shape == (B * S, H * hd)
     with torch.cuda.device(qkv.device):
-        _lib.check(lib.plipmi_attention(code, impl, _ptr(qkv), _ptr(out), B, S, H, int(causal), _ptr(key_mask),
-                                        _stream_ptr(qkv.device)), "plipmi_attention")
+        if head_dim is None:
+            _lib.check(lib.plipmi_attention(code, impl, _ptr(qkv), _ptr(out), B, S, H, int(causal), _ptr(key_mask),
+                                            _stream_ptr(qkv.device)), "plipmi_attention")
+        else:
+            _lib.check(lib.plipmi_attention_hd(code, impl, _ptr(qkv), _ptr(out), B, S, H, hd, int(causal), _ptr(key_mask),
+                                               _stream_ptr(qkv.device)), "plipmi_attention_hd")
     return out
 
 
@@ -262,43 +270,57 @@ def _f32(*ts):
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
 
 
-def attention_probs(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool = False, key_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``plipmi_attention_probs``: qkv [B*S, 3*H*64] (fp32 / bf16 / f16, scale folded into q) -> fp32 probabilities [B, H, S, S]."""
+def attention_probs(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool = False, key_mask: Optional[torch.Tensor] = None,
+                    head_dim: Optional[int] = None) -> torch.Tensor:
+    """``plipmi_attention_probs``: qkv [B*S, 3*H*64] (fp32 / bf16 / f16, scale folded into q) -> fp32 probabilities [B, H, S, S].
+    With ``head_dim`` (here and in the two summaries below): the ``_hd`` entry, qkv [B*S, 3*H*head_dim]."""
     lib = _lib.load()
-    assert qkv.is_cuda and qkv.is_contiguous() and qkv.shape == (B * S, 3 * H * 64)
+    assert qkv.is_cuda and qkv.is_contiguous() and qkv.shape == (B * S, 3 * H * (64 if head_dim is None else head_dim))
     assert key_mask is None or (key_mask.is_cuda and key_mask.dtype == torch.int64 and key_mask.is_contiguous() and key_mask.shape == (B, S))
     probs = torch.empty((B, H, S, S) if S <= 1024 else (1,), dtype=torch.float32, device=qkv.device)   # S > 1024 is refused before any launch
     with torch.cuda.device(qkv.device):
-        _lib.check(lib.plipmi_attention_probs(_code(qkv.dtype), _ptr(qkv), _ptr(probs), B, S, H, int(causal), _ptr(key_mask), _stream_ptr(qkv.device)),
-                   "plipmi_attention_probs")
+        if head_dim is None:
+            _lib.check(lib.plipmi_attention_probs(_code(qkv.dtype), _ptr(qkv), _ptr(probs), B, S, H, int(causal), _ptr(key_mask), _stream_ptr(qkv.device)),
+                       "plipmi_attention_probs")
+        else:
+            _lib.check(lib.plipmi_attention_probs_hd(_code(qkv.dtype), _ptr(qkv), _ptr(probs), B, S, H, int(head_dim), int(causal), _ptr(key_mask),
+                                                     _stream_ptr(qkv.device)), "plipmi_attention_probs_hd")
     return probs
 
 
 def attention_pooled_rows(qkv: torch.Tensor, rows: torch.Tensor, B: int, S: int, H: int, causal: bool = False,
-                          key_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          key_mask: Optional[torch.Tensor] = None, head_dim: Optional[int] = None) -> torch.Tensor:
     """``plipmi_attention_pooled_rows``: row ``rows[b]`` (int32 [B]) of every head's probabilities -> fp32 [B, H, S]."""
     lib = _lib.load()
-    assert qkv.is_cuda and qkv.is_contiguous() and qkv.shape == (B * S, 3 * H * 64)
+    assert qkv.is_cuda and qkv.is_contiguous() and qkv.shape == (B * S, 3 * H * (64 if head_dim is None else head_dim))
     assert rows.is_cuda and rows.dtype == torch.int32 and rows.is_contiguous() and rows.shape == (B,)
     assert key_mask is None or (key_mask.is_cuda and key_mask.dtype == torch.int64 and key_mask.is_contiguous() and key_mask.shape == (B, S))
     out = torch.empty((B, H, S) if S <= 1024 else (1,), dtype=torch.float32, device=qkv.device)
     with torch.cuda.device(qkv.device):
-        _lib.check(lib.plipmi_attention_pooled_rows(_code(qkv.dtype), _ptr(qkv), _ptr(rows), _ptr(out), B, S, H, int(causal), _ptr(key_mask),
-                                                    _stream_ptr(qkv.device)), "plipmi_attention_pooled_rows")
+        if head_dim is None:
+            _lib.check(lib.plipmi_attention_pooled_rows(_code(qkv.dtype), _ptr(qkv), _ptr(rows), _ptr(out), B, S, H, int(causal), _ptr(key_mask),
+                                                        _stream_ptr(qkv.device)), "plipmi_attention_pooled_rows")
+        else:
+            _lib.check(lib.plipmi_attention_pooled_rows_hd(_code(qkv.dtype), _ptr(qkv), _ptr(rows), _ptr(out), B, S, H, int(head_dim), int(causal),
+                                                           _ptr(key_mask), _stream_ptr(qkv.device)), "plipmi_attention_pooled_rows_hd")
     return out
 
 
 def attention_rollout_step(qkv: torch.Tensor, R_in: Optional[torch.Tensor], B: int, S: int, H: int, causal: bool = False,
-                           key_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                           key_mask: Optional[torch.Tensor] = None, head_dim: Optional[int] = None) -> torch.Tensor:
     """``plipmi_attention_rollout_step``: (1/2 mean_h P + 1/2 I) . R_in -> a new fp32 [B, S, S]; ``R_in`` None = the identity."""
     lib = _lib.load()
-    assert qkv.is_cuda and qkv.is_contiguous() and qkv.shape == (B * S, 3 * H * 64)
+    assert qkv.is_cuda and qkv.is_contiguous() and qkv.shape == (B * S, 3 * H * (64 if head_dim is None else head_dim))
     assert R_in is None or (R_in.is_cuda and R_in.dtype == torch.float32 and R_in.is_contiguous() and R_in.shape == (B, S, S))
     assert key_mask is None or (key_mask.is_cuda and key_mask.dtype == torch.int64 and key_mask.is_contiguous() and key_mask.shape == (B, S))
     out = torch.empty((B, S, S) if S <= 1024 else (1,), dtype=torch.float32, device=qkv.device)
     with torch.cuda.device(qkv.device):
-        _lib.check(lib.plipmi_attention_rollout_step(_code(qkv.dtype), _ptr(qkv), _ptr(R_in), _ptr(out), B, S, H, int(causal),
-                                                     _ptr(key_mask), _stream_ptr(qkv.device)), "plipmi_attention_rollout_step")
+        if head_dim is None:
+            _lib.check(lib.plipmi_attention_rollout_step(_code(qkv.dtype), _ptr(qkv), _ptr(R_in), _ptr(out), B, S, H, int(causal),
+                                                         _ptr(key_mask), _stream_ptr(qkv.device)), "plipmi_attention_rollout_step")
+        else:
+            _lib.check(lib.plipmi_attention_rollout_step_hd(_code(qkv.dtype), _ptr(qkv), _ptr(R_in), _ptr(out), B, S, H, int(head_dim), int(causal),
+                                                            _ptr(key_mask), _stream_ptr(qkv.device)), "plipmi_attention_rollout_step_hd")
     return out
 
 

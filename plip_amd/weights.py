@@ -224,8 +224,14 @@ def is_openai_state_dict(sd: Mapping[str, object]) -> bool:
     return "visual.conv1.weight" in sd or "visual.proj" in sd
 
 
+# open_clip's published vision towers whose heads are NOT 64 wide, by (width, layers) -> heads: ViT-H/14 (heads of 80), ViT-g/14 (88),
+# ViT-bigG/14 (104).  An OpenAI-layout state dict does not store the head count; ``width // 64`` -- OpenAI's own rule -- would turn
+# ViT-H/14 into 20 heads of 64, which loads, runs and gives wrong embeddings.
+OPENCLIP_VISION_HEADS = {(1280, 32): 16, (1408, 40): 16, (1664, 48): 16}
+
+
 def config_from_openai_state_dict(sd: Mapping[str, object]) -> PlipConfig:
-    """Recover the architecture the way OpenAI ``clip.model.build_model`` does."""
+    """Recover the architecture the way OpenAI ``clip.model.build_model`` does (vision heads: ``OPENCLIP_VISION_HEADS`` first)."""
     conv = sd["visual.conv1.weight"]
     v_width, _, patch, _ = conv.shape
     v_tokens = sd["visual.positional_embedding"].shape[0]
@@ -239,7 +245,7 @@ def config_from_openai_state_dict(sd: Mapping[str, object]) -> PlipConfig:
     v_mlp = sd["visual.transformer.resblocks.0.mlp.c_fc.weight"].shape[0]
     t_mlp = sd["transformer.resblocks.0.mlp.c_fc.weight"].shape[0]
     return PlipConfig(image_size=grid * patch, patch_size=patch, v_width=v_width, v_layers=v_layers,
-                      v_heads=v_width // 64, v_mlp=v_mlp, vocab_size=vocab, context_length=ctx,
+                      v_heads=OPENCLIP_VISION_HEADS.get((v_width, v_layers), v_width // 64), v_mlp=v_mlp, vocab_size=vocab, context_length=ctx,
                       t_width=t_width, t_layers=t_layers, t_heads=t_width // 64, t_mlp=t_mlp,
                       projection_dim=proj, eos_token_id=2)  # OpenAI pools at argmax(ids)
 
