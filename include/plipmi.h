@@ -317,6 +317,31 @@ int plipmi_encode_tower_outputs(plipmi_handle h, int tower, const void* input, c
 int plipmi_encode_attention_summary(plipmi_handle h, int tower, const void* input, const int64_t* attention_mask, int B, int eos_token_id,
                                     float* pooled_attention, float* rollout, float* rollout_matrix, void* stream);
 
+/* Dense image-text similarity -- one score per token (CLS + every patch) and text prompt: "where in this tile is <prompt>?".
+ * With X [B*S, Dv] the vision encoder's output for B <= max_batch images (pixels fp32 [B,3,H,W] at the handle's size, as
+ * plipmi_encode_image; handles of plipmi_clone_resolution included) let
+ *   E = post_layernorm(X) . visual_projection^T   on EVERY row, [B,S,P], computed in fp32 on every engine dtype (LayerNorm in fp32,
+ *       the projection on the exact-fp32 MFMA GEMM against the fp32 weights the pooled head uses).
+ *   token_embeds : fp32 [B,S,P], optional (may be NULL): E, un-normalised -- HF visual_projection(vision_model.post_layernorm(
+ *                  vision_model(pixel_values).last_hidden_state))
+ *   similarity   : fp32 [B,S,C], optional (may be NULL): similarity[b,s,c] = scale * <E[b,s] / |E[b,s]|, t_c / |t_c|>.  Row s = 0 is the
+ *                  CLS token: what logits_per_image holds for the image (at scale = exp(logit_scale)).  softmax != 0: the softmax over c
+ *                  of those values, max-subtracted.
+ *   text_embeds  : fp32 [C,P] on the device, 16-byte aligned, 1 <= C <= PLIPMI_TOKEN_SIM_MAX_C; the rows need not be normalised.  No
+ *                  epsilon anywhere: a zero row (of E or of text_embeds) gives non-finite scores, as with plipmi_l2_normalize.
+ * The walk is plipmi_encode_tower_outputs' for the vision tower: eager, every block dense on every token.  Behind it run a LayerNorm
+ * over all B*S rows, the projection GEMM and ONE kernel (csrc/token_scores.hip) that forms |E|^2, the C dot products, both
+ * normalisations, the scale and the softmax per row with fixed-order sums: a row's bits depend on neither B nor its place in the batch.
+ * The text rows are normalised inside that kernel, in LDS; the LayerNorm'd rows and -- when token_embeds is NULL -- E live in handle
+ * scratch outside the tower workspace, reserved on first use and freed by plipmi_destroy (clones and resolution handles own theirs).
+ * No handle setting is written, and the encode entries return the same bits after the call as before.
+ * PLIPMI_ERR_INVALID, with a message that names the argument, before any launch: a null handle (checked first), null pixels or
+ * text_embeds, both outputs NULL, C outside 1 .. PLIPMI_TOKEN_SIM_MAX_C, B > max_batch, a projection_dim that is no multiple of 32.
+ * B == 0 is PLIPMI_OK and launches nothing. */
+#define PLIPMI_TOKEN_SIM_MAX_C 64
+int plipmi_encode_token_similarity(plipmi_handle h, const float* pixels, int B, const float* text_embeds, int C,
+                                   float scale, int softmax, float* token_embeds, float* similarity, void* stream);
+
 /* in-place row-wise x / sqrt(sum x^2), no epsilon (modeling_clip.py:57-65) */
 int plipmi_l2_normalize(plipmi_handle h, float* x, int N, int D, void* stream);
 

@@ -222,6 +222,12 @@ int plipmi_attention_pooled_rows_hd(int dtype, const void* qkv, const int32_t* r
 int plipmi_attention_rollout_step_hd(int dtype, const void* qkv, const float* R_in, float* R_out, int B, int S, int H, int head_dim,
                                      int causal, const int64_t* key_mask, void* stream);
 
+/* The scores kernel behind the token-similarity entry of plipmi.h (csrc/token_scores.hip) on its own, for tests/test_gpu_token_similarity.py:
+ * out fp32 [M, C] = scale * <E[m] / |E[m]|, T[c] / |T[c]|> for E fp32 [M, P] and T fp32 [C, P] (rows of any norm, no epsilon); softmax != 0:
+ * the max-subtracted softmax of those values over c.  P % 32 == 0, 32 <= P <= 1024; 1 <= C <= 64; E and T 16-byte aligned device buffers.
+ * Anything else is PLIPMI_ERR_INVALID before any launch; M == 0 launches nothing.  Nothing synchronises. */
+int plipmi_token_scores(const float* E, int M, int P, const float* T, int C, float scale, int softmax, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

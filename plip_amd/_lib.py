@@ -67,6 +67,7 @@ class KernelStat(C.Structure):
 
 
 PROBE_MAX_K = 64     # include/plipmi.h PLIPMI_PROBE_MAX_K
+TOKEN_SIM_MAX_C = 64   # include/plipmi.h PLIPMI_TOKEN_SIM_MAX_C
 
 
 class ProbeInfo(C.Structure):
@@ -116,6 +117,7 @@ TEST_SYMBOLS = {
     "plipmi_attention_probs_hd": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "plipmi_attention_pooled_rows_hd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "plipmi_attention_rollout_step_hd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "plipmi_token_scores": (_i, [_vp, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
 }
 # every symbol include/plipmi.h declares (the product interface): (restype, argtypes)
 SYMBOLS = {
@@ -145,6 +147,7 @@ SYMBOLS = {
     "plipmi_tower_shape": (_i, [_vp, _i, C.POINTER(C.c_int32)]),
     "plipmi_encode_tower_outputs": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "plipmi_encode_attention_summary": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "plipmi_encode_token_similarity": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, _vp, _vp, _vp]),
     "plipmi_probe_fit": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _f, _i, _f, _vp, C.POINTER(ProbeInfo), _vp]),
     "plipmi_probe_predict": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "plipmi_profile_enable": (_i, [_vp, _i]),

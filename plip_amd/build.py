@@ -24,7 +24,9 @@ SOURCES = ["engine.hip", "towers.hip", "heads.hip", "test_entries.hip", "gemm.hi
            # places in the link order are those of a build without them)
            "gemm_gelu_f32.hip", "gemm_gelu_bf16.hip", "gemm_gelu_f16.hip", "gemm_skinny_gelu.hip",
            # attention at head sizes other than 64, likewise behind everything that existed
-           "attention_valu_hd.hip", "attention_mfma_hd.hip", "attention_probs_hd.hip"]
+           "attention_valu_hd.hip", "attention_mfma_hd.hip", "attention_probs_hd.hip",
+           # the per-token image-text scores, likewise
+           "token_scores.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-Wno-unused-value"]
 

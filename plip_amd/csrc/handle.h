@@ -279,6 +279,9 @@ struct plipmi_engine {
   // plipmi_encode_attention_summary scratch: the pooled-row indices and the rollout's two [B, S, S] buffers (allocated on first
   // use, grown on demand; never part of the tower workspace)
   plipmi::Buffer summary_ws;
+  // plipmi_encode_token_similarity scratch: the post_layernorm'd rows [B*S, Dv] and, when the caller takes no token_embeds, their
+  // projections [B*S, P] (allocated on first use, grown on demand; never part of the tower workspace)
+  plipmi::Buffer token_ws;
   // linear-probe scratch (plipmi_probe_fit / _predict / _loss_grad): device partials + results, and a pinned host mirror of the
   // trial point, gradient and losses.  Allocations of their own, grown on demand: never part of the tower workspace.
   plipmi::Buffer probe_ws, probe_host{plipmi::Buffer::kPinned};

@@ -181,6 +181,15 @@ hipError_t launch_attention_rollout_step_hd(const void* qkv, const float* R_in, 
                                             int causal, const int64_t* key_mask, hipStream_t s, const int* rows, float* pooled_out);
 hipError_t launch_attention_rollout_row(const float* R, const int* rows, float* out, int B, int S, hipStream_t s);
 
+// ===== token_scores.hip =====
+// Dense image-text scores (token_scores.hip, plipmi_encode_token_similarity only): out fp32 [M, C] = scale * <E[m] / |E[m]|, T[c] / |T[c]|>
+// for token embeddings E [M, P] and text embeddings T [C, P] (fp32, rows of any norm, no epsilon), softmax != 0: the max-subtracted
+// softmax of those values over c.  P % 32 == 0, 32 <= P <= 1024; 1 <= C <= kTokenSimMaxC; E and T 16-byte aligned.  Fixed-order sums: a
+// row's bits depend on neither M nor the row's place.  Dynamic LDS: token_scores_lds_bytes(P) (sixteen text rows at a time).
+constexpr int kTokenSimMaxC = 64;
+size_t token_scores_lds_bytes(int P);
+hipError_t launch_token_scores(const float* E, int M, int P, const float* T, int C, float scale, int softmax, float* out, hipStream_t s);
+
 // ===== probe.hip =====
 // Linear-probe head (probe.hip): one loss-and-gradient evaluation of the K one-vs-rest logistic problems at WB [K, D + 1] (weights,
 // then intercept) over X [N, D] fp32 with int32 labels y: problem k's positive label is class_base + k, its sample weights pos_w[k] /

@@ -362,6 +362,16 @@ int plipmi_gemm_patch_gather(int dtype, const float* pixels, const uint8_t* tile
   return PLIPMI_OK;
 }
 
+int plipmi_token_scores(const float* E, int M, int P, const float* T, int C, float scale, int softmax, float* out, void* stream) {
+  if (M < 0) return fail(PLIPMI_ERR_INVALID, "M = %d rows", M);
+  if (P < 32 || P > 1024 || P % 32) return fail(PLIPMI_ERR_INVALID, "P = %d: a multiple of 32, 32 .. 1024", P);
+  if (C < 1 || C > kTokenSimMaxC) return fail(PLIPMI_ERR_INVALID, "C = %d text rows: 1 .. %d", C, kTokenSimMaxC);
+  if (!E || !T || !out) return fail(PLIPMI_ERR_INVALID, "null E / T / out");
+  if ((reinterpret_cast<uintptr_t>(E) | reinterpret_cast<uintptr_t>(T)) % 16) return fail(PLIPMI_ERR_INVALID, "E / T must be 16-byte aligned");
+  HIP_TRY(launch_token_scores(E, M, P, T, C, scale, softmax, out, reinterpret_cast<hipStream_t>(stream)));
+  return PLIPMI_OK;
+}
+
 int plipmi_gemm_variant_built(int dtype, int variant) {
   if (!valid_dtype(dtype)) return 0;
   return gemm_variant_is_built(dtype, variant) ? 1 : 0;

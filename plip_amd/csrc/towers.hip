@@ -547,4 +547,52 @@ int plipmi_encode_attention_summary(plipmi_handle h, int tower, const void* inpu
   return PLIPMI_OK;
 }
 
+// Dense image-text similarity (include/plipmi.h): the vision walk of plipmi_encode_tower_outputs, then the pooled head's arithmetic on
+// EVERY row -- post_layernorm, the fp32 projection -- and the scores kernel (token_scores.hip).  The LayerNorm'd rows and an E nobody
+// asked for live in handle scratch of their own (token_ws), outside the tower workspace.
+int plipmi_encode_token_similarity(plipmi_handle h, const float* pixels, int B, const float* text_embeds, int C, float scale, int softmax,
+                                   float* token_embeds, float* similarity, void* stream) {
+  static_assert(PLIPMI_TOKEN_SIM_MAX_C == kTokenSimMaxC, "the header's limit is the kernel's");
+  RUN(check_batch(h, B));
+  if (C < 1 || C > PLIPMI_TOKEN_SIM_MAX_C) return fail(PLIPMI_ERR_INVALID, "C = %d text rows: 1 .. %d", C, PLIPMI_TOKEN_SIM_MAX_C);
+  if (B == 0) return PLIPMI_OK;
+  if (!pixels) return fail(PLIPMI_ERR_INVALID, "null pixels");
+  if (!text_embeds) return fail(PLIPMI_ERR_INVALID, "null text_embeds");
+  if (reinterpret_cast<uintptr_t>(text_embeds) % 16) return fail(PLIPMI_ERR_INVALID, "text_embeds must be 16-byte aligned");
+  if (!token_embeds && !similarity) return fail(PLIPMI_ERR_INVALID, "no output buffer given (token_embeds and similarity are both NULL)");
+  const int P = h->cfg().projection_dim;
+  if (P % 32) return fail(PLIPMI_ERR_INVALID, "projection_dim = %d: the per-token head takes multiples of 32", P);
+  if (token_embeds && reinterpret_cast<uintptr_t>(token_embeds) % 16) return fail(PLIPMI_ERR_INVALID, "token_embeds must be 16-byte aligned");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Forward f(h, PLIPMI_VISION, B, nullptr, s, Forward::kEveryToken, /*may_pack=*/false);
+  const int M = f.M(), D = f.m.D;
+  const size_t ln_bytes = align_up((size_t)M * D * sizeof(float), 256);
+  RUN(h->token_ws.reserve(ln_bytes + (token_embeds ? 0 : (size_t)M * P * sizeof(float)), s));
+  float* ln = reinterpret_cast<float*>(h->token_ws.data());
+  float* E = token_embeds ? token_embeds : reinterpret_cast<float*>(h->token_ws.data() + ln_bytes);
+  RUN(embed(f, pixels, false, -1));
+  RUN(run_layers(f, f.m.L));   // t.x = the encoder output, fp32
+  { Scope sc(h, s, "layernorm", 0, (double)M * D * 8);
+    HIP_TRY(launch_layernorm(f.t.x, D, f.m.head_ln_w, f.m.head_ln_b, ln, 0, M, D, h->cfg().layer_norm_eps, s)); }
+  {
+    // one tile for every M (the 128 x 128 one; projections narrower than that: the 32 x 32 tile of the pooled head), so that a row's
+    // bits do not depend on the batch it travels in
+    const char* name = "head_gemm";
+    Scope sc(h, s, name, 2.0 * M * P * (double)D, ((double)M * D + (double)P * D + (double)M * P) * 4);
+    if (P % 128 == 0) {
+      const GemmParams p = make_params(ln, f.m.proj, E, nullptr, M, P, D, D, D, P);
+      const int rc = gemm_launch(PLIPMI_F32, EPI_SCALE, 1, p, s, &name);
+      if (rc != 0) return fail(PLIPMI_ERR_HIP, "token projection gemm (M=%d N=%d K=%d) failed: %s", M, P, D, hipGetErrorString((hipError_t)rc));
+    } else {
+      HIP_TRY(launch_head_gemm(ln, f.m.proj, E, M, P, D, s));
+    }
+    if (h->prof.on) sc.rename(name_with_role(name, "token_proj"));
+  }
+  if (similarity) {
+    Scope sc(h, s, "token_scores", 2.0 * M * (double)P * (C + 1), ((double)M * P + (double)C * P + (double)M * C) * 4);
+    HIP_TRY(launch_token_scores(E, M, P, text_embeds, C, scale, softmax, similarity, s));
+  }
+  return PLIPMI_OK;
+}
+
 }  // extern "C"

@@ -588,3 +588,23 @@ def attention_packed(qkv: torch.Tensor, out: torch.Tensor, cu: torch.Tensor, S: 
         _lib.check(lib.plipmi_attention_packed(_code(qkv.dtype), int(impl), _ptr(qkv), _ptr(out), B, int(S), H, int(causal), _ptr(key_mask),
                                                _ptr(cu), _stream_ptr(qkv.device)), "plipmi_attention_packed")
     return out
+
+
+def token_scores(E: torch.Tensor, T: torch.Tensor, scale: float = 1.0, softmax: bool = False, out: Optional[torch.Tensor] = None,
+                 M: Optional[int] = None) -> torch.Tensor:
+    """``plipmi_token_scores``: E fp32 [M, P], T fp32 [C, P] -> fp32 [M, C] = scale * cosine, or its softmax over C.  ``out``: a
+    contiguous fp32 buffer of at least [M, C] whose first M rows are written (the tests put guard rows behind them); ``M``: fewer rows
+    than E holds."""
+    lib = _lib.load()
+    assert E.is_cuda and T.is_cuda and E.dtype == T.dtype == torch.float32 and E.is_contiguous() and T.is_contiguous()
+    assert E.dim() == 2 and T.dim() == 2 and E.shape[1] == T.shape[1]
+    M = E.shape[0] if M is None else int(M)
+    C, P = T.shape
+    assert 0 <= M <= E.shape[0]
+    if out is None:
+        out = torch.empty((M, C), dtype=torch.float32, device=E.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= M * C
+    with torch.cuda.device(E.device):
+        _lib.check(lib.plipmi_token_scores(_ptr(E), M, int(P), _ptr(T), int(C), float(scale), int(bool(softmax)), _ptr(out),
+                                           _stream_ptr(E.device)), "plipmi_token_scores")
+    return out

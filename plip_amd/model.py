@@ -24,7 +24,8 @@ import torch
 from . import weights as W
 from .config import PlipConfig, get_config
 from .engine import Engine
-from .outputs import AttentionSummary, TowerOutput
+from .outputs import AttentionSummary, TokenSimilarity, TowerOutput
+from .token_similarity import token_similarity
 
 
 @dataclass
@@ -65,6 +66,15 @@ class _Tower:
         ``text_model.attention_summary(input_ids, attention_mask=None, ...)``: ``Engine.attention_summary`` of this tower (keywords
         ``pooled_attention``, ``rollout``, ``rollout_matrix``, ``eos_token_id``)."""
         return self._model._vision_summary(*args, **kw) if self._vision else self._model._text_summary(*args, **kw)
+
+    @torch.no_grad()
+    def token_similarity(self, *args, **kw) -> TokenSimilarity:
+        """``vision_model.token_similarity(pixel_values, text_embeds, interpolate_pos_encoding=False, ...)``: per token and text row the
+        scaled cosine of the token's projected embedding with the text embedding (``plip_amd.token_similarity.token_similarity``;
+        keywords ``scale``, ``softmax``, ``return_embeds``).  The vision tower only."""
+        if not self._vision:
+            raise ValueError("token_similarity scores image tokens against text embeddings: call it on vision_model")
+        return self._model._vision_token_similarity(*args, **kw)
 
 
 class PlipModel:
@@ -160,6 +170,12 @@ class PlipModel:
         if pixel_values is None:
             raise ValueError("You have to specify pixel_values")
         return self._image_engine(pixel_values, interpolate_pos_encoding).attention_summary("vision", pixel_values, **summary_options)
+
+    def _vision_token_similarity(self, pixel_values=None, text_embeds=None, interpolate_pos_encoding: bool = False,
+                                 **options) -> TokenSimilarity:
+        if pixel_values is None or text_embeds is None:
+            raise ValueError("You have to specify pixel_values and text_embeds")
+        return token_similarity(self._image_engine(pixel_values, interpolate_pos_encoding), pixel_values, text_embeds, **options)
 
     def _text_summary(self, input_ids=None, attention_mask=None, **summary_options) -> AttentionSummary:
         if input_ids is None:

@@ -1,6 +1,7 @@
 """Per-token tower outputs: the ``BaseModelOutputWithPooling`` of HF ``CLIPVisionTransformer`` / ``CLIPTextTransformer``
 (``last_hidden_state``, ``pooler_output``, ``hidden_states``, ``attentions``) and the buffer arithmetic of
-``plipmi_encode_tower_outputs`` (include/plipmi.h); the attention summaries of ``plipmi_encode_attention_summary``.  No GPU needed here."""
+``plipmi_encode_tower_outputs`` (include/plipmi.h); the attention summaries of ``plipmi_encode_attention_summary``; the per-token
+image-text scores of ``plipmi_encode_token_similarity``.  No GPU needed here."""
 from __future__ import annotations
 
 from dataclasses import dataclass, fields
@@ -68,3 +69,23 @@ def attention_summary_bytes(B: int, S: int, H: int, L: int, pooled_attention: bo
             "rollout": 4 * B * S if rollout else 0,
             "rollout_matrix": 4 * B * S * S if rollout_matrix else 0,
             "scratch": 4 * B + (4 * B * S * S * (1 if rollout_matrix else 2) if roll else 0)}
+
+
+@dataclass
+class TokenSimilarity:
+    """``plip_amd.token_similarity.token_similarity`` (include/plipmi.h plipmi_encode_token_similarity), fp32 on the GPU.
+    ``similarity``: [B,S,C], per token (row 0 = CLS, then the patches row-major) and text row the scaled cosine, or its softmax over C;
+    ``token_embeds``: [B,S,P], the un-normalised projected embedding of every token -- None unless asked for."""
+    similarity: Optional[torch.Tensor] = None
+    token_embeds: Optional[torch.Tensor] = None
+
+
+def token_similarity_bytes(B: int, S: int, D: int, P: int, C: int, token_embeds: bool = False) -> dict:
+    """fp32 bytes of each buffer ``plipmi_encode_token_similarity`` writes for B images of S tokens (vision width D, projection P, C text
+    rows; 0 for a token_embeds nobody asked for) and of the handle scratch one call of B images reserves: similarity [B,S,C],
+    token_embeds [B,S,P]; scratch = the post_layernorm'd rows [B,S,D] (rounded up to 256 bytes) plus E [B,S,P] when the caller takes
+    no token_embeds."""
+    ln = (4 * B * S * D + 255) // 256 * 256
+    return {"similarity": 4 * B * S * C,
+            "token_embeds": 4 * B * S * P if token_embeds else 0,
+            "scratch": ln + (0 if token_embeds else 4 * B * S * P)}

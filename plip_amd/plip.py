@@ -33,6 +33,7 @@ import torch
 from .image_routes import PinnedPair, consume_routed_batch, encode_direct, lane_loop, open_paths, prepare_routed_batch
 from .model import PlipModel
 from .preprocess import load_tokenizer, preprocess_images
+from .token_similarity import token_similarity
 
 # The top-level reference class preprocesses with HF ``CLIPProcessor`` (plip.py:27,35), whose centre crop starts at
 # ``(extent - n) // 2``; the reproducibility/ embedders use torchvision's rounding instead (preprocess.crop_offset).
@@ -149,6 +150,31 @@ class PLIP:
                 outs.append(row[:, 1:].reshape(-1, gh, gw))
         if not outs:
             return np.zeros((0, gh, gw), np.float32)
+        return torch.cat(outs).detach().cpu().numpy()
+
+    def similarity_maps(self, images: Union[List[str], list, np.ndarray, torch.Tensor], text, batch_size: int,
+                        image_size: Optional[int] = None, softmax: bool = False, scale: Optional[float] = None) -> np.ndarray:
+        """(extension) One map per image and prompt over the patch grid, float32 [N, C, gh, gw]: the cosine of every patch token's
+        projected embedding with the prompt's text embedding, times ``scale`` (include/plipmi.h ``plipmi_encode_token_similarity``) --
+        or, with ``softmax``, the softmax of those values over the C prompts of each patch.  ``text``: a list of prompts (needs the
+        tokenizer), token ids [C, context_length], or a ready float [C, P] array of text embeddings (any norm); at most 64 prompts.
+        ``scale`` None: 1.0, or ``exp(logit_scale)`` with ``softmax``.  The CLS row is dropped.  Images are handled exactly as in
+        ``attention_maps``."""
+        n_px = self.model.config.image_size if image_size is None else int(image_size)
+        eng = self.model.engine if image_size is None else self.model.engine.at_resolution(n_px, n_px)
+        gh = gw = n_px // self.model.config.patch_size
+        ready = (torch.is_tensor(text) and text.is_floating_point()) or (isinstance(text, np.ndarray) and text.dtype.kind == "f")
+        txt = torch.as_tensor(text if ready else self.encode_text(text, batch_size=max(int(batch_size), 1)))
+        if scale is None:
+            scale = float(np.exp(float(self.model.logit_scale))) if softmax else 1.0
+        outs = []
+        with torch.no_grad():
+            for s in range(0, len(images), batch_size):
+                px = _attention_pixels(open_paths(images[s:s + batch_size]), n_px)
+                sim = token_similarity(eng, px, txt, scale=scale, softmax=softmax).similarity
+                outs.append(sim[:, 1:].transpose(1, 2).reshape(sim.shape[0], sim.shape[2], gh, gw))
+        if not outs:
+            return np.zeros((0, int(txt.shape[0]), gh, gw), np.float32)
         return torch.cat(outs).detach().cpu().numpy()
 
     _stages = None           # tile size -> pinned uint8 [max_batch, n, n, 3] staging rows of the direct loop (allocated on first use)
