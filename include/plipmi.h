@@ -24,6 +24,8 @@
  *   plipmi_similarity_topk<- the same two call sites, fused with the dot product (no [N,N] matrix)
  *   plipmi_probe_fit      <- SGDClassifier(loss="log_loss", ...).fit(train_x, train_y)   reproducibility/evaluation/linear_probing/linear_classifier.py:18-31
  *   plipmi_probe_predict  <- classifier.predict(x)                                       linear_classifier.py:32-33
+ *   plipmi_softmax_fit    <- LinearClassifier + nn.CrossEntropyLoss() on a frozen tower         reproducibility/fine_tuning/finetune.py
+ *                            (and the CLIP paper's LogisticRegression(C=0.316, max_iter=1000).fit(train_x, train_y))
  *
  * Conventions
  *   - plain C, no torch / HIP types in the signatures: device buffers are raw
@@ -431,6 +433,29 @@ int plipmi_probe_fit(plipmi_handle h, const float* X, int N, int D, const int32_
                      float alpha, int max_iter, float gtol, float* WB_inout, plipmi_probe_info* info_out, void* stream);
 int plipmi_probe_predict(plipmi_handle h, const float* X, int N, int D, const float* WB, int K, float* decision, int32_t* pred,
                          void* stream);
+
+/* ---- softmax (multinomial) linear probe ----------------------------------------
+ * (Additive, like the entries above it: the version number and every existing entry are unchanged; a caller probes for the symbol.)
+ * The other linear-probe objective, ONE softmax over all classes -- the CLIP paper's protocol, scikit-learn's
+ * LogisticRegression(C, max_iter=1000) (multinomial, L-BFGS), and the reference's own fine-tuning head (LinearClassifier +
+ * nn.CrossEntropyLoss(), reproducibility/fine_tuning/finetune.py) with the tower frozen:
+ *   f(W, b) = (1/N) sum_i cw[y_i] (logsumexp_k(x_i.w_k + b_k) - (x_i.w_{y_i} + b_{y_i})) + alpha/2 |W|_F^2
+ * for C >= 2 classes, always C rows (no special two-class shape); the intercepts are not regularised; alpha = 1 / (C_sklearn N).
+ *   X, y     as plipmi_probe_fit.  A label outside [0, C) gives its row weight 0 (the host checks the range).
+ *   class_w  fp32 [C] device: cw (class_weight="balanced": N / (C count_k)), or NULL = all ones
+ *   WB       fp32 [C, D + 1] device: row k = w_k, then b_k.  2 <= C <= PLIPMI_PROBE_MAX_K.
+ * Three or more classes: the minimiser is LogisticRegression(C = 1 / (alpha N), class_weight)'s.  f does not change when a constant
+ * is added to every intercept; the gradient with respect to b sums to zero, so a fit from zeros stays on sum(b) = 0 up to rounding
+ * (compare b - mean(b)), and the columns of the optimal W sum to zero.  Two classes: W[1] - W[0] and b[1] - b[0] are
+ * LogisticRegression(C = 2 / (alpha N))'s binary coef_ and intercept_ (the two-row softmax is the binary problem at HALF the penalty).
+ * plipmi_softmax_fit minimises f from the point in WB_inout and leaves the result there: one L-BFGS (10 pairs, backtracking line
+ * search, on the host) over all C (D + 1) variables, one loss-and-gradient evaluation per trial point (csrc/probe_softmax.hip: fp32
+ * MFMA, X read once per evaluation for C <= 16 and 1 + ceil(C / 16) times beyond, fixed-order reductions -- the same inputs give the
+ * same bits).  Like plipmi_probe_fit it SYNCHRONISES the stream once per evaluation, stops when |grad f|_inf <= gtol, and returns
+ * PLIPMI_ERR_NOT_CONVERGED with the best point found after max_iter iterations.  info_out (may be NULL) keeps its layout: loss[0] = f,
+ * converged is 0 or 1.  Scratch is the handle's probe scratch.  Predictions and decision values: plipmi_probe_predict on WB, K = C. */
+int plipmi_softmax_fit(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int C, const float* class_w, float alpha,
+                       int max_iter, float gtol, float* WB_inout, plipmi_probe_info* info_out, void* stream);
 
 /* ---- measurement ------------------------------------------------------------
  * (kernel-level test entries and A/B hooks live in plipmi_test.h: same library, not part of the product interface) */

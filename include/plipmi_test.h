@@ -228,6 +228,12 @@ int plipmi_attention_rollout_step_hd(int dtype, const void* qkv, const float* R_
  * Anything else is PLIPMI_ERR_INVALID before any launch; M == 0 launches nothing.  Nothing synchronises. */
 int plipmi_token_scores(const float* E, int M, int P, const float* T, int C, float scale, int softmax, float* out, void* stream);
 
+/* One evaluation of the softmax probe's objective (csrc/probe_softmax.hip; arguments as plipmi_softmax_fit in plipmi.h) at WB [C, D + 1],
+ * for tests/test_gpu_softmax_probe.py: loss_out double [1] = f, grad_out fp32 [C, D + 1] = its gradient (weights, then intercept), both
+ * device buffers.  Enqueues only. */
+int plipmi_softmax_loss_grad(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int C, const float* class_w, float alpha,
+                             const float* WB, double* loss_out, float* grad_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,7 @@ TEST_SYMBOLS = {
     "plipmi_attention_pooled_rows_hd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "plipmi_attention_rollout_step_hd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "plipmi_token_scores": (_i, [_vp, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
+    "plipmi_softmax_loss_grad": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp]),
 }
 # every symbol include/plipmi.h declares (the product interface): (restype, argtypes)
 SYMBOLS = {
@@ -150,6 +151,7 @@ SYMBOLS = {
     "plipmi_encode_token_similarity": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, _vp, _vp, _vp]),
     "plipmi_probe_fit": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _f, _i, _f, _vp, C.POINTER(ProbeInfo), _vp]),
     "plipmi_probe_predict": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "plipmi_softmax_fit": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _f, _i, _f, _vp, C.POINTER(ProbeInfo), _vp]),
     "plipmi_profile_enable": (_i, [_vp, _i]),
     "plipmi_profile_read": (_i, [_vp, C.POINTER(KernelStat), _i, C.POINTER(_i)]),
 }

@@ -26,7 +26,9 @@ SOURCES = ["engine.hip", "towers.hip", "heads.hip", "test_entries.hip", "gemm.hi
            # attention at head sizes other than 64, likewise behind everything that existed
            "attention_valu_hd.hip", "attention_mfma_hd.hip", "attention_probs_hd.hip",
            # the per-token image-text scores, likewise
-           "token_scores.hip"]
+           "token_scores.hip",
+           # the softmax (multinomial) linear probe's loss-and-gradient pass, likewise
+           "probe_softmax.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-Wno-unused-value"]
 

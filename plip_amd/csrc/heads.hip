@@ -1,5 +1,5 @@
 // heads.hip -- what runs on embeddings and images outside the towers: L2 normalisation, logits, top-k and the streaming
-// similarity top-k, the Pillow-exact resize entries, and the linear-probe driver (probe.hip, probe_solver.h).
+// similarity top-k, the Pillow-exact resize entries, and the linear-probe drivers (probe.hip, probe_softmax.hip, probe_solver.h).
 #include <algorithm>
 #include <cmath>
 
@@ -248,6 +248,83 @@ int plipmi_probe_predict(plipmi_handle h, const float* X, int N, int D, const fl
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Scope sc(h, s, "probe_predict", 2.0 * N * (double)D * K, (double)N * D * 4);
   HIP_TRY(launch_probe_predict(X, N, D, WB, K, decision, pred, s));
+  return PLIPMI_OK;
+}
+
+// ---- softmax linear probe (probe_softmax.hip, probe_solver.h) ------------------------------------------------------------------
+static int softmax_check(plipmi_handle h, const void* X, int N, int D, const void* y, int C, float alpha, const void* WB) {
+  if (!h || !X || !y || !WB) return fail(PLIPMI_ERR_INVALID, "null handle / X / y / WB");
+  if (N <= 0) return fail(PLIPMI_ERR_INVALID, "need N > 0 rows, got %d", N);
+  if (C < 2 || C > PLIPMI_PROBE_MAX_K) return fail(PLIPMI_ERR_INVALID, "need 2 <= C <= %d classes, got %d", PLIPMI_PROBE_MAX_K, C);
+  if (D < 4 || D > 1024 || D % 4) return fail(PLIPMI_ERR_INVALID, "embedding width %d unsupported (D %% 4 == 0, 4 <= D <= 1024)", D);
+  if (reinterpret_cast<uintptr_t>(X) % 16) return fail(PLIPMI_ERR_INVALID, "X must be 16-byte aligned");
+  if (!std::isfinite(alpha) || alpha <= 0.f) return fail(PLIPMI_ERR_INVALID, "alpha must be finite and > 0, got %g", (double)alpha);
+  return PLIPMI_OK;
+}
+static int softmax_eval(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int C, const float* class_w, float alpha,
+                        const float* WB, float** grad, double** loss, hipStream_t s) {
+  const int passes = C <= 16 ? 1 : 1 + (C + 15) / 16;      // over X
+  Scope sc(h, s, "softmax_loss_grad", 4.0 * N * (double)D * 16 * ((C + 15) / 16) + (C > 16 ? 2.0 * N * (double)D * C : 0.0),
+           (double)N * D * 4 * passes);
+  HIP_TRY(launch_softmax_loss_grad(X, N, D, y, WB, C, class_w, alpha, h->probe_ws.data(), grad, loss, s));
+  return PLIPMI_OK;
+}
+
+int plipmi_softmax_loss_grad(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int C, const float* class_w, float alpha,
+                             const float* WB, double* loss_out, float* grad_out, void* stream) {
+  RUN(softmax_check(h, X, N, D, y, C, alpha, WB));
+  if (!loss_out || !grad_out) return fail(PLIPMI_ERR_INVALID, "null loss_out / grad_out");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  RUN(h->probe_ws.reserve(softmax_scratch_bytes(N, D, C), s));
+  float* grad; double* loss;
+  RUN(softmax_eval(h, X, N, D, y, C, class_w, alpha, WB, &grad, &loss, s));
+  HIP_TRY(hipMemcpyAsync(grad_out, grad, (size_t)C * (D + 1) * 4, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(loss_out, loss, 8, hipMemcpyDeviceToDevice, s));
+  return PLIPMI_OK;
+}
+
+int plipmi_softmax_fit(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int C, const float* class_w, float alpha,
+                       int max_iter, float gtol, float* WB_inout, plipmi_probe_info* info_out, void* stream) {
+  RUN(softmax_check(h, X, N, D, y, C, alpha, WB_inout));
+  if (max_iter < 1 || !std::isfinite(gtol) || gtol <= 0.f) return fail(PLIPMI_ERR_INVALID, "need max_iter >= 1 and a finite gtol > 0");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  RUN(h->probe_ws.reserve(softmax_scratch_bytes(N, D, C), s));
+  const int n = C * (D + 1);                 // ONE problem over all the variables: the classes are coupled
+  const size_t wb_bytes = (size_t)n * 4;
+  RUN(h->probe_host.reserve(2 * align_up(wb_bytes, 256) + 256, s));
+  float* wb_h = reinterpret_cast<float*>(h->probe_host.data());
+  float* g_h = reinterpret_cast<float*>(h->probe_host.data() + align_up(wb_bytes, 256));
+  double* l_h = reinterpret_cast<double*>(h->probe_host.data() + 2 * align_up(wb_bytes, 256));
+
+  HIP_TRY(hipMemcpyAsync(wb_h, WB_inout, wb_bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(wb_h[i])) return fail(PLIPMI_ERR_INVALID, "the starting point WB_inout holds a non-finite value");
+  ProbeLbfgs prob;
+  prob.init(wb_h, n, max_iter, (double)gtol);
+  int evals = 0;
+  // one evaluation per trial point; the trial point travels through WB_inout itself
+  for (;;) {
+    prob.trial(wb_h);
+    HIP_TRY(hipMemcpyAsync(WB_inout, wb_h, wb_bytes, hipMemcpyHostToDevice, s));
+    if (prob.done) break;            // WB_inout now holds the final point
+    float* grad; double* loss;
+    RUN(softmax_eval(h, X, N, D, y, C, class_w, alpha, WB_inout, &grad, &loss, s));
+    HIP_TRY(hipMemcpyAsync(g_h, grad, wb_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(l_h, loss, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ++evals;
+    prob.feed(*l_h, g_h);
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  if (info_out) {
+    memset(info_out, 0, sizeof(*info_out));
+    info_out->iterations = prob.iters; info_out->evaluations = evals; info_out->converged = prob.converged ? 1 : 0;
+    info_out->grad_norm = prob.gnorm; info_out->loss[0] = prob.f;
+  }
+  if (!prob.converged)
+    return fail(PLIPMI_ERR_NOT_CONVERGED, "softmax fit: did not reach |grad|_inf <= %g within %d iterations (now %g, %d evaluations); "
+                "WB holds the best point found", (double)gtol, max_iter, prob.gnorm, evals);
   return PLIPMI_OK;
 }
 

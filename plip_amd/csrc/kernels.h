@@ -202,6 +202,16 @@ hipError_t launch_probe_loss_grad(const float* X, int N, int D, const int32_t* y
 // decision [N, K] = X W^T + b (may be nullptr) and pred [N] = first arg-max over the K problems (K == 1: z > 0)
 hipError_t launch_probe_predict(const float* X, int N, int D, const float* WB, int K, float* decision, int32_t* pred, hipStream_t s);
 
+// ===== probe_softmax.hip =====
+// Softmax (multinomial) linear probe: one loss-and-gradient evaluation of f(W, b) = (1/N) sum_i cw[y_i] (logsumexp_k z_ik - z_iy) +
+// alpha/2 |W|_F^2 at WB [C, D + 1] over X [N, D] fp32 with int32 labels y; class_w fp32 [C] or nullptr = ones; a label outside [0, C)
+// gives its row weight 0.  `scratch` (softmax_scratch_bytes) holds the per-workgroup partials, the rows' statistics (C > 16) and the
+// results: *grad = fp32 [C, D + 1], *loss = double [1] point into it.  D % 4 == 0, D <= 1024, 2 <= C <= 64, X 16-byte aligned.
+// C <= 16: X is read once; else 1 + ceil(C / 16) times.  Deterministic: fixed-order reductions.
+size_t softmax_scratch_bytes(int N, int D, int C);
+hipError_t launch_softmax_loss_grad(const float* X, int N, int D, const int32_t* y, const float* WB, int C, const float* class_w,
+                                    float alpha, char* scratch, float** grad, double** loss, hipStream_t s);
+
 // ===== resize_ragged.hip =====
 // The same resize + crop for a RAGGED batch (resize_ragged.hip): B images of their own sizes packed in src at offsets[b] (device int64),
 // hw int32 [B, 2] on the device; geometry, coefficient tables and the layout of the intermediate are computed on the device inside

@@ -4,6 +4,7 @@
 // is the evaluation: every pass of probe_loss_grad_kernel evaluates all K current trial points at once.  A problem is fed the
 // loss and gradient at its trial point and answers with its next one (a shorter step along the same direction, or a step along a
 // new direction); a problem that has finished keeps handing out its final point.
+// plipmi_softmax_fit runs ONE such machine over all C (D + 1) variables: a softmax couples the classes (probe_softmax.hip).
 //
 // Line search: backtracking from the unit step (first iteration: 1 / |g|), the next trial from the secant of the directional
 // derivative.  A step is accepted on the Armijo condition, or -- close to the minimum, where differences of f drown in the

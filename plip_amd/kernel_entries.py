@@ -264,6 +264,25 @@ def probe_loss_grad(engine, x: torch.Tensor, y: torch.Tensor, wb: torch.Tensor, 
     return loss, grad
 
 
+def softmax_loss_grad(engine, x: torch.Tensor, y: torch.Tensor, wb: torch.Tensor, class_w: Optional[torch.Tensor], alpha: float):
+    """One evaluation of the softmax probe's objective (include/plipmi_test.h ``plipmi_softmax_loss_grad``): x fp32 [N, D], y int32 [N],
+    wb fp32 [C, D + 1], class_w fp32 [C] or None (ones), all on the engine's device -> (loss double [1], grad fp32 [C, D + 1]).  The
+    outputs are filled with NaN first, so an element the kernels do not write shows."""
+    lib = _lib.load()
+    for t, dt in ((x, torch.float32), (y, torch.int32), (wb, torch.float32)) + (() if class_w is None else ((class_w, torch.float32),)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous()
+    N, D = x.shape
+    C = wb.shape[0]
+    assert wb.shape[1] == D + 1 and y.shape == (N,) and (class_w is None or class_w.shape == (C,))
+    loss = torch.full((1,), float("nan"), dtype=torch.float64, device=x.device)
+    grad = torch.full((C, D + 1), float("nan"), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.plipmi_softmax_loss_grad(engine._h, _ptr(x), N, D, _ptr(y), C, _ptr(class_w), float(alpha), _ptr(wb),
+                                                _ptr(loss), _ptr(grad), _stream_ptr(x.device)),
+                   "plipmi_softmax_loss_grad")
+    return loss, grad
+
+
 # ---- the kernels around the GEMMs (include/plipmi_test.h, tests/test_gpu_small_kernels.py) ---------------------------------------------
 def _f32(*ts):
     for t in ts:

@@ -11,6 +11,8 @@ reproducibility/evaluation/zero_shot/zero_shot.py      :class:`evaluation.ZeroSh
 reproducibility/evaluation/retrieval/retrieval.py      :class:`evaluation.ImageRetrieval`
 reproducibility/evaluation/linear_probing/             :class:`linear_probe.LinearProber`
 reproducibility/metrics.py                             :mod:`metrics`
+reproducibility/fine_tuning/finetune.py (frozen tower:
+``LinearClassifier`` + ``nn.CrossEntropyLoss()``)      :class:`softmax_probe.SoftmaxProber`
 =====================================================  ==========================================
 
 The towers, the normalisation, the similarity product, the arg-max, the top-50 and the linear probe's
@@ -22,3 +24,4 @@ from .embedders import CLIPEmbedder, EmbedderFactory  # noqa: F401
 from .evaluation import ImageRetrieval, ZeroShotClassifier  # noqa: F401
 from .linear_probe import LinearProber  # noqa: F401
 from .metrics import eval_metrics, retrieval_metrics  # noqa: F401
+from .softmax_probe import SoftmaxProber  # noqa: F401
