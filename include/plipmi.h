@@ -26,6 +26,8 @@
  *   plipmi_probe_predict  <- classifier.predict(x)                                       linear_classifier.py:32-33
  *   plipmi_softmax_fit    <- LinearClassifier + nn.CrossEntropyLoss() on a frozen tower         reproducibility/fine_tuning/finetune.py
  *                            (and the CLIP paper's LogisticRegression(C=0.316, max_iter=1000).fit(train_x, train_y))
+ *   plipmi_region_select, plipmi_region_gather <- nothing in the reference, which takes tiles somebody has already cut: the grid,
+ *                            the background filter and the stacking its users do in numpy in front of encode_images
  *
  * Conventions
  *   - plain C, no torch / HIP types in the signatures: device buffers are raw
@@ -389,6 +391,33 @@ int plipmi_resize_crop_u8_ragged(plipmi_handle h, const uint8_t* src, size_t src
                                  void* workspace, size_t workspace_bytes, uint8_t* dst, void* stream);
 /* bytes of `workspace` for that call (0 for a bad argument); host arithmetic only */
 size_t plipmi_resize_ragged_workspace(const int32_t* hw_host, int B, int n_px, int ksize);
+
+/* ---- slide regions ---------------------------------------------------------
+ * (Additive: the version number and every existing entry are unchanged; a caller probes for the symbols.)
+ * A slide region on the device -- uint8 RGB, H rows of W pixels, row y at region + y * pitch_bytes (pitch_bytes >= 3 W: a view of a
+ * larger array works as it is; rows may start at any byte) -- cut into a grid of tile x tile windows, tile (i, j) with its top-left
+ * pixel at (y0 + i * stride, x0 + j * stride), flat index i * cols + j.  stride < tile overlaps, stride > tile leaves gaps.  The
+ * caller states rows and cols; every tile must lie inside the region (rows = (H - y0 - tile) / stride + 1 is the most that fit).
+ *
+ * plipmi_region_select: counts[i * cols + j] = the tile's pixels that are tissue, by integer arithmetic only (the same numbers on every
+ * platform; numpy restatement: plip_amd/preprocess.py tissue_mask).  With mx / mn the largest / smallest of r, g, b and
+ * luma = (77 r + 150 g + 29 b + 128) >> 8, a pixel is tissue iff 255 (mx - mn) >= sat_min * mx and luma_min <= luma <= luma_max
+ * (each threshold 0 .. 255).  kept[0 .. K) = the flat indices of the tiles with counts >= min_count, ascending; *n_kept = K; the rest
+ * of kept is not written.  counts, kept int32 [rows * cols], n_kept int32 [1], all on the device.  Two launches, no allocation, no
+ * synchronisation.  rows * cols == 0 launches nothing and sets *n_kept = 0.
+ *
+ * plipmi_region_gather: dst[b] = tile kept[first + b] for b in 0 .. B, dst uint8 [B, tile, tile, 3] contiguous -- the batch the u8
+ * encode entry (tile = the engine's image size) or plipmi_resize_crop_u8 takes.  kept is device memory (plipmi_region_select's, or any
+ * int32 list of flat indices); first + B <= rows * cols with rows the most that fit.  An index outside the grid is clamped to it on
+ * the device: wrong pixels, never an address outside the region.  One launch; B == 0 launches nothing.
+ *
+ * Both return PLIPMI_ERR_INVALID with a message before any launch: a null pointer, a tile outside the H x W region, pitch_bytes < 3 W,
+ * a region of 4 GiB or more (H * pitch_bytes; pass it in bands), a threshold outside 0 .. 255, a negative min_count / first / B. */
+int plipmi_region_select(plipmi_handle h, const uint8_t* region, int H, int W, int64_t pitch_bytes, int y0, int x0, int tile, int stride,
+                         int rows, int cols, int sat_min, int luma_min, int luma_max, int min_count, int32_t* counts, int32_t* kept,
+                         int32_t* n_kept, void* stream);
+int plipmi_region_gather(plipmi_handle h, const uint8_t* region, int H, int W, int64_t pitch_bytes, int y0, int x0, int tile, int stride,
+                         int cols, const int32_t* kept, int first, int B, uint8_t* dst, void* stream);
 
 /* Fused similarity + top-k: for every row q of keys [Nq,D] the k rows j of space [Ns,D] with the largest <q, space_j>,
  * descending (ties: lower j first), WITHOUT materialising the [Nq,Ns] score matrix: scores are produced in

@@ -28,7 +28,9 @@ SOURCES = ["engine.hip", "towers.hip", "heads.hip", "test_entries.hip", "gemm.hi
            # the per-token image-text scores, likewise
            "token_scores.hip",
            # the softmax (multinomial) linear probe's loss-and-gradient pass, likewise
-           "probe_softmax.hip"]
+           "probe_softmax.hip",
+           # the slide-region entries and their kernels (tissue count, compaction, tile gather), likewise
+           "region.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-Wno-unused-value"]
 

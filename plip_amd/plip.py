@@ -177,6 +177,26 @@ class PLIP:
             return np.zeros((0, int(txt.shape[0]), gh, gw), np.float32)
         return torch.cat(outs).detach().cpu().numpy()
 
+    def encode_region(self, region, tile_px: Optional[int] = None, stride: Optional[int] = None, origin=(0, 0),
+                      min_tissue: float = 0.5, sat_min: int = 18, luma_min: int = 25, luma_max: int = 235,
+                      image_size: Optional[int] = None, band_rows: Optional[int] = None):
+        """(extension) A slide region -> the embeddings of its tissue tiles; the grid, the background filter and the stacking run on the
+        GPU (region_routes.py).  ``region``: uint8 [H,W,3] -- a device tensor (any row stride: a view of a larger array is read where it
+        is), or a numpy array / ``np.memmap`` / PIL image on the host, uploaded in bands of ``band_rows`` whole tile-rows (default: what a
+        quarter of the free device memory holds; the result does not depend on it).  Tiles of ``tile_px`` pixels (default: the encode
+        resolution) every ``stride`` pixels (default ``tile_px``; smaller overlaps, larger leaves gaps) from ``origin`` = (y0, x0); tiles
+        that do not fit are dropped.  A tile is kept when at least ``ceil(min_tissue * tile_px ** 2)`` of its pixels are tissue
+        (``preprocess.tissue_mask``: ``sat_min``, ``luma_min``, ``luma_max``, each 0 .. 255).  Kept tiles of another size than the encode
+        resolution are resized on the GPU exactly as ``encode_images`` resizes a host list of such crops; ``image_size`` selects the
+        resolution as it does there.  Returns a ``RegionEmbeddings``: ``embeddings`` float32 [K,P] (un-normalised, bit for bit what
+        ``encode_images`` gives for the same crops), ``coords`` int64 [K,2], ``kept`` int64 [K], ``grid`` (rows, cols), ``tissue``
+        float32 [rows, cols].  An empty grid or a region without tissue gives K = 0."""
+        from .region_routes import encode_region
+        n_px = self.model.config.image_size if image_size is None else int(image_size)
+        eng = self.model.engine if image_size is None else self.model.engine.at_resolution(n_px, n_px)
+        return encode_region(eng, region, n_px, self.model.config.projection_dim, _CROP, tile_px=tile_px, stride=stride, origin=origin,
+                             min_tissue=min_tissue, sat_min=sat_min, luma_min=luma_min, luma_max=luma_max, band_rows=band_rows)
+
     _stages = None           # tile size -> pinned uint8 [max_batch, n, n, 3] staging rows of the direct loop (allocated on first use)
 
     def _fill_stage(self, tiles, n_px, cap) -> torch.Tensor:

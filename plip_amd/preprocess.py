@@ -214,6 +214,67 @@ def resize_crop_ragged_reference(images: Sequence, n_px: int = 224, crop: str = 
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# Slide regions (plipmi_region_select / plipmi_region_gather): the tissue rule and the tile grid, written ONCE here in numpy.  The
+# kernels restate them (csrc/region.hip) and the tests hold the kernels to these functions; the rule is integer arithmetic only, so
+# there is nothing to round.
+# ---------------------------------------------------------------------------------------------------------------
+TISSUE_DEFAULTS = dict(sat_min=18, luma_min=25, luma_max=235)
+
+
+def check_tissue_thresholds(sat_min: int, luma_min: int, luma_max: int) -> None:
+    for name, v in (("sat_min", sat_min), ("luma_min", luma_min), ("luma_max", luma_max)):
+        if int(v) != v or not 0 <= int(v) <= 255:
+            raise ValueError(f"{name} must be an integer in 0 .. 255, got {v!r}")
+
+
+def tissue_mask(rgb: np.ndarray, sat_min: int = 18, luma_min: int = 25, luma_max: int = 235) -> np.ndarray:
+    """uint8 [..., 3] RGB -> bool [...]: a pixel is tissue iff it is coloured enough, ``255 (mx - mn) >= sat_min * mx`` with ``mx`` /
+    ``mn`` the largest / smallest of its channels, and neither dark nor blank, ``luma_min <= (77 r + 150 g + 29 b + 128) >> 8 <=
+    luma_max``.  Glass is bright and grey, pen marks and the slide's edge are dark."""
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.shape[-1] != 3:
+        raise ValueError(f"tissue_mask takes uint8 [..., 3], got {rgb.dtype} {rgb.shape}")
+    check_tissue_thresholds(sat_min, luma_min, luma_max)
+    x = rgb.astype(np.int32)
+    mx, mn = x.max(axis=-1), x.min(axis=-1)
+    luma = (77 * x[..., 0] + 150 * x[..., 1] + 29 * x[..., 2] + 128) >> 8
+    return (255 * (mx - mn) >= int(sat_min) * mx) & (luma >= int(luma_min)) & (luma <= int(luma_max))
+
+
+def region_grid(H: int, W: int, tile_px: int, stride: int, origin=(0, 0)):
+    """``(rows, cols)`` of the tiles of ``tile_px`` pixels, one every ``stride``, that fit an ``H x W`` region from ``origin`` =
+    (y0, x0): tile (i, j) has its top-left pixel at (y0 + i * stride, x0 + j * stride) and the flat index i * cols + j; tiles that do
+    not fit are dropped; either number is 0 when not even one fits."""
+    y0, x0 = (int(v) for v in origin)
+    t, s = int(tile_px), int(stride)
+    if t < 1 or s < 1 or y0 < 0 or x0 < 0:
+        raise ValueError(f"tile_px {tile_px}, stride {stride}, origin {origin}: need tile_px >= 1, stride >= 1 and an origin >= (0, 0)")
+    rows = (int(H) - y0 - t) // s + 1 if int(H) - y0 - t >= 0 else 0
+    cols = (int(W) - x0 - t) // s + 1 if int(W) - x0 - t >= 0 else 0
+    return rows, cols
+
+
+def region_min_count(min_tissue: float, tile_px: int) -> int:
+    """The tissue pixels a tile of ``tile_px`` needs to be kept: ``ceil(min_tissue * tile_px ** 2)``, never below 0."""
+    import math
+    if not min_tissue == min_tissue:
+        raise ValueError("min_tissue is NaN")
+    return max(0, min(int(math.ceil(float(min_tissue) * int(tile_px) ** 2)), 2 ** 31 - 1))
+
+
+def region_tile_counts(region: np.ndarray, tile_px: int, stride: int, origin=(0, 0), **thresholds) -> np.ndarray:
+    """The oracle of ``plipmi_region_select``'s counts: int32 [rows, cols], tissue pixels per tile of :func:`region_grid`."""
+    rows, cols = region_grid(region.shape[0], region.shape[1], tile_px, stride, origin)
+    mask = tissue_mask(region, **thresholds)
+    out = np.zeros((rows, cols), np.int32)
+    for i in range(rows):
+        for j in range(cols):
+            y, x = origin[0] + i * stride, origin[1] + j * stride
+            out[i, j] = int(mask[y:y + tile_px, x:x + tile_px].sum())
+    return out
+
+
 def preprocess_images(images: Sequence, n_px: int = 224, crop: str = "torchvision") -> np.ndarray:
     return np.stack([preprocess_image(i, n_px, crop) for i in images]) if len(images) else \
         np.zeros((0, 3, n_px, n_px), np.float32)
