@@ -28,6 +28,8 @@
  *                            (and the CLIP paper's LogisticRegression(C=0.316, max_iter=1000).fit(train_x, train_y))
  *   plipmi_region_select, plipmi_region_gather <- nothing in the reference, which takes tiles somebody has already cut: the grid,
  *                            the background filter and the stacking its users do in numpy in front of encode_images
+ *   plipmi_warp_u8        <- RandomCrop + RandomHorizontalFlip + RandomAffine, then RandomPerspective      reproducibility/embedders/transform.py
+ *                            (_train_transform; one call per stage, PIL's Image.transform bytes)
  *
  * Conventions
  *   - plain C, no torch / HIP types in the signatures: device buffers are raw
@@ -418,6 +420,37 @@ int plipmi_region_select(plipmi_handle h, const uint8_t* region, int H, int W, i
                          int32_t* n_kept, void* stream);
 int plipmi_region_gather(plipmi_handle h, const uint8_t* region, int H, int W, int64_t pitch_bytes, int y0, int x0, int tile, int stride,
                          int cols, const int32_t* kept, int first, int B, uint8_t* dst, void* stream);
+
+/* ---- augmented views --------------------------------------------------------
+ * (Additive: the version number and every existing entry are unchanged; a caller probes for the symbol.)
+ * plipmi_warp_u8: dst[b] (uint8 [B, out_h, out_w, 3] contiguous) = source image b warped by coefficient row b, with the bytes of
+ * Pillow's Image.transform((out_w, out_h), AFFINE | PERSPECTIVE, coeffs, BILINEAR, fillcolor=...) -- the call torchvision's
+ * RandomAffine / RandomPerspective / F.affine / F.perspective make on a PIL image (reproducibility/embedders/transform.py
+ * _train_transform).  Source image b is uint8 RGB, H rows of W pixels, row y at src + b * image_stride_bytes + y * pitch_bytes
+ * (pitch_bytes >= 3 W; rows and images may start at any byte); image_stride_bytes == 0: all B outputs sample the ONE image at src (V
+ * views of a tile, its eight dihedral views).  coeffs double [B,8] ON THE DEVICE: the output -> input map of output pixel (x, y), in
+ * fp64 with every product and sum rounded once in the order written (numpy restatement: plip_amd/preprocess.py warp_reference):
+ *     xin = x + 0.5, yin = y + 0.5
+ *     perspective == 0:  xs = (a0 xin + a1 yin) + a2,  ys = (a3 xin + a4 yin) + a5                   (a6, a7 are not read)
+ *     perspective == 1:  the same two, each divided by den = (a6 xin + a7 yin) + 1
+ * windows int32 [B,5] on the device, or NULL: (wy, wx, wh, ww, flip) -- the image that is sampled is rows wy .. wy + wh, columns wx ..
+ * wx + ww of the source, mirrored left-right when flip != 0 (crop, flip and warp in one pass, bytes equal to doing them in turn);
+ * NULL = the whole source, not mirrored.  A point with 0 <= xs < ww and 0 <= ys < wh is sampled bilinearly at (xs - 0.5, ys - 0.5)
+ * with the columns and the first row clipped to the window and the result truncated to a byte; every other point (NaN included) gets
+ * fill_rgb = r | g << 8 | b << 16.
+ * Read on the device and REFUSED there, not clamped: a window that does not lie inside the H x W source (wy, wx < 0, wh, ww < 1, wy +
+ * wh > H, wx + ww > W), and with perspective == 1 a row whose den is not > 0 at the four corners (0, 0), (out_w, 0), (0, out_h),
+ * (out_w, out_h) of the output (den is linear, so it is then > 0 at every pixel; Pillow leaves a vanishing den undefined).  Such an
+ * image comes out all fill and no address outside the source is formed; the call still returns PLIPMI_OK.  The entry cannot read
+ * the rows without synchronising, so it does not: callers that hold them on the host refuse such rows by name before they are uploaded (plip_amd/preprocess.py
+ * check_perspective, plip_amd/augment.py).
+ * One launch, no allocation, no synchronisation; B == 0 launches nothing.  PLIPMI_ERR_INVALID with a message before any launch: a
+ * null handle / src / coeffs / dst, B < 0, a side < 1, pitch_bytes < 3 W, image_stride_bytes < 0, a source image (H * pitch_bytes) or
+ * an output image (3 out_h out_w) of 2 GiB or more (the kernel's offsets inside one image are 32-bit), perspective other than 0 / 1,
+ * bits of fill_rgb above the third byte, coeffs not 8-byte / windows not 4-byte aligned. */
+int plipmi_warp_u8(plipmi_handle h, const uint8_t* src, int B, int H, int W, int64_t pitch_bytes, int64_t image_stride_bytes,
+                   const int32_t* windows, const double* coeffs, int perspective, int out_h, int out_w, uint32_t fill_rgb, uint8_t* dst,
+                   void* stream);
 
 /* Fused similarity + top-k: for every row q of keys [Nq,D] the k rows j of space [Ns,D] with the largest <q, space_j>,
  * descending (ties: lower j first), WITHOUT materialising the [Nq,Ns] score matrix: scores are produced in

@@ -145,6 +145,7 @@ SYMBOLS = {
     "plipmi_resize_ragged_workspace": (C.c_size_t, [_vp, _i, _i, _i]),
     "plipmi_region_select": (_i, [_vp, _vp, _i, _i, C.c_int64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "plipmi_region_gather": (_i, [_vp, _vp, _i, _i, C.c_int64, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "plipmi_warp_u8": (_i, [_vp, _vp, _i, _i, _i, C.c_int64, C.c_int64, _vp, _vp, _i, _i, _i, C.c_uint32, _vp, _vp]),
     "plipmi_similarity_topk": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "plipmi_set_text_packing": (_i, [_vp, _i]),
     "plipmi_tower_shape": (_i, [_vp, _i, C.POINTER(C.c_int32)]),

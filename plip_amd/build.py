@@ -29,6 +29,8 @@ SOURCES = ["engine.hip", "towers.hip", "heads.hip", "test_entries.hip", "gemm.hi
            "token_scores.hip",
            # the softmax (multinomial) linear probe's loss-and-gradient pass, likewise
            "probe_softmax.hip",
+           # the augmented-view entry and its kernel (Pillow-exact affine / perspective warp in fp64), likewise
+           "augment.hip",
            # the slide-region entries and their kernels (tissue count, compaction, tile gather), likewise
            "region.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",

@@ -197,6 +197,31 @@ class PLIP:
         return encode_region(eng, region, n_px, self.model.config.projection_dim, _CROP, tile_px=tile_px, stride=stride, origin=origin,
                              min_tissue=min_tissue, sat_min=sat_min, luma_min=luma_min, luma_max=luma_max, band_rows=band_rows)
 
+    def encode_views(self, images, batch_size: int, views: int = 8, transform: str = "d4", seed: int = 0, reduce: Optional[str] = None,
+                     return_params: bool = False):
+        """(extension) Embeddings of ``views`` augmented views of every tile, the views built on the GPU (augment.py; Pillow-exact
+        warps, include/plipmi.h ``plipmi_warp_u8``) inside the lane that encodes them.  ``images``: uint8 RGB tiles of ONE size -- an
+        array or tensor [N,H,W,3] (a device tensor is read where it is) or a list of arrays / PIL images.  ``transform``:
+
+        ``"d4"``     the symmetries of the square in the order of ``preprocess.dihedral_coeffs`` (view 0 is the tile itself), ``views``
+                     <= 8; tiles at the encode resolution.  Exact re-indexing: test-time augmentation over orientations.
+        ``"train"``  the reference's ``_train_transform`` (reproducibility/embedders/transform.py): a random n_px crop, a horizontal
+                     flip, ``RandomAffine(10, translate .1, scale (.8, 1.2), shear +-15, BILINEAR, fill 127)`` and
+                     ``RandomPerspective(0.3, p=0.3)``, each stage through bytes as the PIL chain; tiles with H, W >= n_px.  Its
+                     first step, ``Resize([512])``, is NOT done here: it is the resize route ``encode_images`` and
+                     ``Engine.resize_crop_u8`` already have -- resize first where the tiles are not at the size to crop from.  The
+                     draws of view v of tile i come from ``np.random.default_rng([seed, i, v])`` (``preprocess.sample_train_params``):
+                     they do not depend on ``batch_size``, the order of the calls or the lane, and nothing claims torch's stream.
+
+        Returns float32 [N, views, P], un-normalised rows, each bit for bit what ``encode_images`` gives for that view's bytes;
+        ``reduce="mean"``: float32 [N, P], the L2-normalised mean over the views of the L2-normalised rows.  ``return_params``: also the
+        ``(windows [N,V,5], affine [N,V,8], perspective [N,V,8])`` rows the views were made with (``preprocess.train_view_reference`` /
+        ``warp_reference`` regenerate their bytes).  ``batch_size`` tiles (times ``views`` rows) go to a lane at a time.  ValueError
+        before anything is uploaded or launched: mixed sizes, tiles smaller than n_px, ``views`` > 8 for "d4", an unknown transform."""
+        from .augment import encode_views
+        return encode_views(self.model.engine, images, batch_size, self.model.config.image_size, self.model.config.projection_dim, views=views,
+                            transform=transform, seed=seed, reduce=reduce, return_params=return_params)
+
     _stages = None           # tile size -> pinned uint8 [max_batch, n, n, 3] staging rows of the direct loop (allocated on first use)
 
     def _fill_stage(self, tiles, n_px, cap) -> torch.Tensor:

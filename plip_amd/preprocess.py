@@ -275,6 +275,189 @@ def region_tile_counts(region: np.ndarray, tile_px: int, stride: int, origin=(0,
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# Augmented views (include/plipmi.h plipmi_warp_u8, plip_amd/augment.py).  The reference's ``_train_transform``
+# (reproducibility/embedders/transform.py:18-38) is RandomCrop -> RandomHorizontalFlip -> RandomAffine -> RandomPerspective on PIL
+# images, and torchvision warps a PIL image with ``Image.transform(size, AFFINE | PERSPECTIVE, coeffs, BILINEAR, fillcolor=...)``.
+# ``warp_reference`` restates that call (libImaging/Geometry.c: affine_transform / perspective_transform, bilinear_filter8) in numpy
+# float64 -- every product and sum rounds once, as in the C -- and is the oracle of the kernel; the builders below are torchvision's
+# ``_get_inverse_affine_matrix`` / ``_get_perspective_coeffs`` and the parameter ranges of the reference.  torchvision is not a
+# dependency: these functions are the specification, and nothing claims parity with torch's random stream.
+def check_perspective(coeffs, out_h: int, out_w: int) -> np.ndarray:
+    """float64 [..., 8] perspective rows for an ``out_h x out_w`` output, refused by name (ValueError) when the denominator
+    ``(a6 x + a7 y) + 1`` is not > 0 at the four corners (0, 0), (out_w, 0), (0, out_h), (out_w, out_h): it is linear, so it is then
+    > 0 at every pixel.  Pillow leaves a denominator that vanishes inside the output undefined; such rows never reach a kernel."""
+    a = np.asarray(coeffs, dtype=np.float64)
+    if a.shape[-1] != 8:
+        raise ValueError(f"perspective rows have 8 coefficients, got {a.shape}")
+    with np.errstate(invalid="ignore", over="ignore"):
+        ok = np.ones(a.shape[:-1], bool)
+        for X, Y in ((0.0, 0.0), (float(out_w), 0.0), (0.0, float(out_h)), (float(out_w), float(out_h))):
+            ok &= ((a[..., 6] * X + a[..., 7] * Y) + 1.0) > 0.0
+    if not ok.all():
+        bad = np.argwhere(~np.atleast_1d(ok))[0].tolist()
+        raise ValueError(f"vanishing denominator: perspective row {bad} has (a6 x + a7 y) + 1 <= 0 (or not finite) at a corner of the "
+                         f"{out_h} x {out_w} output")
+    return a
+
+
+def warp_reference(src: np.ndarray, coeffs, perspective: bool = False, out_size=None, fill=127, window=None) -> np.ndarray:
+    """The oracle of ``plipmi_warp_u8`` for one image: uint8 [H,W,3] -> uint8 [oh,ow,3], byte for byte
+    ``Image.fromarray(img).transform((ow, oh), AFFINE | PERSPECTIVE, coeffs, BILINEAR, fillcolor=fill)`` where ``img`` is the
+    ``window`` = (wy, wx, wh, ww, flip) of ``src``, mirrored left-right when ``flip`` (default: all of ``src``).  ``coeffs``: 6 or 8
+    float64 (affine reads the first six), the output -> input map of include/plipmi.h; ``fill`` an int or (r, g, b)."""
+    src = np.asarray(src)
+    if src.dtype != np.uint8 or src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError(f"warp_reference takes uint8 [H,W,3], got {src.dtype} {src.shape}")
+    a = np.zeros(8, np.float64)
+    c = np.asarray(coeffs, dtype=np.float64).reshape(-1)
+    if c.size not in (6, 8) or (perspective and c.size != 8):
+        raise ValueError(f"{c.size} coefficients: an affine row has 6 (or 8), a perspective row 8")
+    a[:c.size] = c
+    oh, ow = (src.shape[0], src.shape[1]) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    if perspective:
+        check_perspective(a, oh, ow)
+    wy, wx, wh, ww, flip = (0, 0, src.shape[0], src.shape[1], 0) if window is None else (int(v) for v in window)
+    if wy < 0 or wx < 0 or wh < 1 or ww < 1 or wy + wh > src.shape[0] or wx + ww > src.shape[1]:
+        raise ValueError(f"window {(wy, wx, wh, ww)} does not lie inside the {src.shape[0]} x {src.shape[1]} source")
+    img = src[wy:wy + wh, wx:wx + ww]
+    if flip:
+        img = img[:, ::-1]
+    fill = np.asarray((fill,) * 3 if np.ndim(fill) == 0 else fill, dtype=np.uint8)
+    xin = (np.arange(ow, dtype=np.float64) + 0.5)[None, :]
+    yin = (np.arange(oh, dtype=np.float64) + 0.5)[:, None]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        xs = (a[0] * xin + a[1] * yin) + a[2]
+        ys = (a[3] * xin + a[4] * yin) + a[5]
+        if perspective:
+            den = (a[6] * xin + a[7] * yin) + 1.0
+            xs, ys = xs / den, ys / den
+        inside = (xs >= 0.0) & (xs < ww) & (ys >= 0.0) & (ys < wh)
+    xs, ys = np.where(inside, xs, 0.5), np.where(inside, ys, 0.5)
+    xf, yf = xs - 0.5, ys - 0.5
+    x0, y0 = np.floor(xf), np.floor(yf)
+    dx, dy = (xf - x0)[..., None], (yf - y0)[..., None]
+    x0, y0 = x0.astype(np.int64), y0.astype(np.int64)
+    c0, c1 = np.clip(x0, 0, ww - 1), np.clip(x0 + 1, 0, ww - 1)
+    r0 = np.clip(y0, 0, wh - 1)
+    second = (y0 + 1 >= 0) & (y0 + 1 < wh)              # row y0 + 1 is not clipped: outside, the first row stands for it
+    r1 = np.where(second, y0 + 1, r0)
+    px = img.astype(np.float64)
+    v1 = px[r0, c0] + (px[r0, c1] - px[r0, c0]) * dx
+    v2 = np.where(second[..., None], px[r1, c0] + (px[r1, c1] - px[r1, c0]) * dx, v1)
+    v = v1 + (v2 - v1) * dy
+    return np.where(inside[..., None], v.astype(np.uint8), fill[None, None, :])        # (truncation; v is in [0, 255])
+
+
+def affine_coeffs(center, angle_deg: float, translate, scale: float, shear_deg) -> np.ndarray:
+    """float64 [6]: the output -> input map of a rotation by ``angle_deg`` about ``center`` = (cx, cy), a shear by ``shear_deg`` =
+    (sx, sy) degrees, a ``scale`` and a translation by ``translate`` = (tx, ty) pixels -- the inverse of translate . centre .
+    rotate-shear-scale . centre^-1, as torchvision's ``_get_inverse_affine_matrix`` writes it (the row ``F.affine`` hands to PIL;
+    for an image of w x h pixels the centre is (w * 0.5, h * 0.5))."""
+    import math
+    cx, cy = (float(v) for v in center)
+    tx, ty = (float(v) for v in translate)
+    rot, sx, sy = math.radians(angle_deg), math.radians(shear_deg[0]), math.radians(shear_deg[1])
+    a = math.cos(rot - sy) / math.cos(sy)
+    b = -math.cos(rot - sy) * math.tan(sx) / math.cos(sy) - math.sin(rot)
+    c = math.sin(rot - sy) / math.cos(sy)
+    d = -math.sin(rot - sy) * math.tan(sx) / math.cos(sy) + math.cos(rot)
+    m = [v / float(scale) for v in (d, -b, 0.0, -c, a, 0.0)]
+    m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty) + cx
+    m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty) + cy
+    return np.asarray(m, dtype=np.float64)
+
+
+def perspective_coeffs(startpoints, endpoints) -> np.ndarray:
+    """float64 [8]: the perspective row with ``start = H(end)`` for four point pairs (x, y) -- the output -> input map that
+    sends each endpoint to its startpoint, torchvision's ``_get_perspective_coeffs`` as an 8 x 8 float64 solve.  Refused by name
+    (ValueError): degenerate points, and a row whose denominator is not > 0 at all four endpoints (the quadrilateral is folded
+    over: the denominator vanishes between its corners)."""
+    s, e = np.asarray(startpoints, np.float64), np.asarray(endpoints, np.float64)
+    if s.shape != (4, 2) or e.shape != (4, 2):
+        raise ValueError(f"perspective_coeffs takes four (x, y) start and end points, got {s.shape} and {e.shape}")
+    A = np.zeros((8, 8), np.float64)
+    for i in range(4):
+        A[2 * i] = [e[i, 0], e[i, 1], 1, 0, 0, 0, -s[i, 0] * e[i, 0], -s[i, 0] * e[i, 1]]
+        A[2 * i + 1] = [0, 0, 0, e[i, 0], e[i, 1], 1, -s[i, 1] * e[i, 0], -s[i, 1] * e[i, 1]]
+    try:
+        a = np.linalg.solve(A, s.reshape(-1))
+    except np.linalg.LinAlgError as err:
+        raise ValueError(f"vanishing denominator: no perspective map sends {e.tolist()} to {s.tolist()} ({err})") from None
+    den = (a[6] * e[:, 0] + a[7] * e[:, 1]) + 1.0
+    if not (np.isfinite(a).all() and (den > 0.0).all()):
+        raise ValueError(f"vanishing denominator: the map from {e.tolist()} to {s.tolist()} has (a6 x + a7 y) + 1 = {den.tolist()} at "
+                         "the endpoints, not > 0 at all four")
+    return a
+
+
+def dihedral_coeffs(k: int, n: int) -> np.ndarray:
+    """float64 [6], integer entries: symmetry ``k`` = 0 .. 7 of an n x n tile as an affine output -> input row.  View k of ``img`` is
+    ``np.rot90(img if k < 4 else img[:, ::-1], k % 4)``: 0 the identity, 1 .. 3 the quarter turns, 4 the left-right flip
+    ``[-1,0,n, 0,1,0]``, 5 .. 7 the flip followed by the turns.  Pixel centres map to pixel centres, so the warp is an exact
+    re-index (dx = dy = 0 in ``warp_reference``)."""
+    k, n = int(k), float(int(n))
+    if not 0 <= k <= 7:
+        raise ValueError(f"a square has eight symmetries, k = 0 .. 7; got {k}")
+    rows = [[1, 0, 0, 0, 1, 0], [0, -1, n, 1, 0, 0], [-1, 0, n, 0, -1, n], [0, 1, 0, -1, 0, n],
+            [-1, 0, n, 0, 1, 0], [0, 1, 0, 1, 0, 0], [1, 0, 0, 0, -1, n], [0, -1, n, -1, 0, n]]
+    return np.asarray(rows[k], dtype=np.float64)
+
+
+IDENTITY_ROW = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0)     # as an affine and as a perspective row: the input's bytes exactly
+
+
+def sample_train_params(seed: int, index: int, view: int, src_hw, n_px: int, degrees: float = 10.0, translate: float = 0.1,
+                        scale=(0.8, 1.2), shear: float = 15.0, p_flip: float = 0.5, distortion: float = 0.3, p_perspective: float = 0.3):
+    """The random draws of the reference's ``_train_transform`` (transform.py:23-38; its ranges are the keyword defaults) for view
+    ``view`` of image ``index`` of ``src_hw`` = (H, W) pixels, H, W >= n_px -> ``(window, affine, perspective)``: int32 [5] (top, left,
+    n_px, n_px, flip), float64 [8] (an affine row, a6 = a7 = 0) and float64 [8] (a perspective row; the identity when none is drawn).
+    Every draw comes from ``np.random.default_rng([seed, index, view])`` in a fixed order, whatever is drawn: a view's bytes depend on
+    (seed, index, view) alone, never on the batch size, the order or the lane.
+    Crop: top, left uniform over the positions that fit.  Flip: p = ``p_flip``.  Affine about the crop's centre (n/2, n/2): angle
+    U(-degrees, degrees); tx, ty = round(U(-translate n, translate n)); scale U(*scale); shears U(-shear, shear) each.  Perspective,
+    p = ``p_perspective``: each corner of [[0,0],[n-1,0],[n-1,n-1],[0,n-1]] moves inward by an integer in [0, d] per axis, d =
+    int(distortion * (n // 2))."""
+    H, W = int(src_hw[0]), int(src_hw[1])
+    n = int(n_px)
+    if n < 1 or H < n or W < n:
+        raise ValueError(f"a crop of {n} px does not fit a source of {H} x {W} pixels")
+    rng = np.random.default_rng([int(seed), int(index), int(view)])
+    top, left = int(rng.integers(0, H - n + 1)), int(rng.integers(0, W - n + 1))
+    flip = int(rng.random() < p_flip)
+    angle = float(rng.uniform(-degrees, degrees))
+    tx, ty = (int(round(float(rng.uniform(-translate * n, translate * n)))) for _ in range(2))
+    sc = float(rng.uniform(scale[0], scale[1]))
+    shx, shy = float(rng.uniform(-shear, shear)), float(rng.uniform(-shear, shear))
+    warp = bool(rng.random() < p_perspective)
+    d = int(distortion * (n // 2))
+    move = rng.integers(0, d + 1, size=(4, 2))
+    affine = np.zeros(8, np.float64)
+    affine[:6] = affine_coeffs((n * 0.5, n * 0.5), angle, (tx, ty), sc, (shx, shy))
+    persp = np.asarray(IDENTITY_ROW, np.float64)
+    if warp:
+        start = np.asarray([[0, 0], [n - 1, 0], [n - 1, n - 1], [0, n - 1]], np.float64)
+        end = start + move * np.asarray([[1, 1], [-1, 1], [-1, -1], [1, -1]], np.float64)
+        persp = check_perspective(perspective_coeffs(start, end), n, n)
+    return np.asarray([top, left, n, n, flip], np.int32), affine, persp
+
+
+def train_params(seed: int, count: int, views: int, src_hw, n_px: int, first: int = 0, **ranges):
+    """``sample_train_params`` for images ``first .. first + count`` and views ``0 .. views`` -> ``(windows int32 [count, views, 5],
+    affine float64 [count, views, 8], perspective float64 [count, views, 8])``."""
+    rows = [[sample_train_params(seed, first + i, v, src_hw, n_px, **ranges) for v in range(int(views))] for i in range(int(count))]
+    shape = (int(count), int(views))
+    return (np.asarray([[r[0] for r in row] for row in rows], np.int32).reshape(shape + (5,)),
+            np.asarray([[r[1] for r in row] for row in rows], np.float64).reshape(shape + (8,)),
+            np.asarray([[r[2] for r in row] for row in rows], np.float64).reshape(shape + (8,)))
+
+
+def train_view_reference(src: np.ndarray, window, affine, perspective, fill=127) -> np.ndarray:
+    """One view of the train chain in numpy, each stage through bytes as the PIL chain goes: crop + flip + affine, then perspective."""
+    n = int(window[2])
+    return warp_reference(warp_reference(src, affine, False, (n, n), fill, window), perspective, True, (n, n), fill)
+
+
 def preprocess_images(images: Sequence, n_px: int = 224, crop: str = "torchvision") -> np.ndarray:
     return np.stack([preprocess_image(i, n_px, crop) for i in images]) if len(images) else \
         np.zeros((0, 3, n_px, n_px), np.float32)
