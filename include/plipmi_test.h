@@ -210,8 +210,9 @@ int plipmi_attention_packed(int dtype, int impl, const void* qkv, void* out, int
 /* The attention entries with the head size as an argument (tests/test_gpu_attention_head_dim.py): plipmi_attention,
  * plipmi_attention_probs, plipmi_attention_pooled_rows and plipmi_attention_rollout_step over qkv [B*S, 3 * H * head_dim] (q | k | v, head
  * h at columns h * head_dim ..; 1/sqrt(head_dim) already folded into q), out [B*S, H * head_dim].  head_dim = 64 is the entry without
- * the argument, the same kernels; 72 .. 128 in steps of 8 run the padded-head kernels (csrc/attention_valu_hd.hip,
- * csrc/attention_mfma_hd.hip: impl 1 is one chunked kernel for every S; csrc/attention_probs_hd.hip).  Anything else is refused with
+ * the argument, the same kernels; 72 .. 128 in steps of 8 run the padded-head kernels of the same units
+ * (csrc/attention.hip; csrc/attention_mfma.hip: impl 1 is one chunked kernel for every S; csrc/attention_probs.hip,
+ * csrc/attention_summary.hip).  Anything else is refused with
  * PLIPMI_ERR_INVALID and a message that names head_dim.  Every other argument and every result as documented for the entry above. */
 int plipmi_attention_hd(int dtype, int impl, const void* qkv, void* out, int B, int S, int H, int head_dim, int causal,
                         const int64_t* key_mask, void* stream);

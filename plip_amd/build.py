@@ -23,9 +23,7 @@ SOURCES = ["engine.hip", "towers.hip", "heads.hip", "test_entries.hip", "gemm.hi
            # the exact-GELU epilogues: units of their own, behind everything that existed (the other units' code objects and their
            # places in the link order are those of a build without them)
            "gemm_gelu_f32.hip", "gemm_gelu_bf16.hip", "gemm_gelu_f16.hip", "gemm_skinny_gelu.hip",
-           # attention at head sizes other than 64, likewise behind everything that existed
-           "attention_valu_hd.hip", "attention_mfma_hd.hip", "attention_probs_hd.hip",
-           # the per-token image-text scores, likewise
+           # the per-token image-text scores, likewise behind everything that existed
            "token_scores.hip",
            # the softmax (multinomial) linear probe's loss-and-gradient pass, likewise
            "probe_softmax.hip",

@@ -1,10 +1,11 @@
 // attention_mfma_dev.h -- the device code the MFMA attention kernels share (attention_mfma.hip: the single-pass kernel for
-// S <= 128 and the chunked online-softmax kernel; qkv_attention.hip: the attention in the fused text kernel's epilogue): the LDS
+// S <= 128 and the two chunked online-softmax kernels; qkv_attention.hip: the attention in the fused text kernel's epilogue): the LDS
 // images of Q / K / V and the steps that turn them into normalised output rows of one block of 32 queries -- fragment reads,
 // mask, P V product, output staging (the products and their layouts: attention_mfma.hip's header comment).  Kernels built from
 // these functions perform the same operations in the same order per query, so they produce the same bits.  Staging, barriers, the
 // live / open tile tests, the exp pass and the LOOPS stay with each kernel: a function here is one step on values (one fragment,
-// one MFMA, one store) -- helpers that held the ks / dt / q4 loops changed the kernels' instructions (profiles/attention_shared_isa.txt).
+// one MFMA, one store) -- helpers that held the ks / dt / q4 loops changed the kernels' instructions (profiles/attention_shared_isa.txt);
+// what the two chunked kernels share beyond these steps, their online-softmax update, is text for that reason: attention_flash_step.inc.
 // A wave works on 32 queries: lane = query lrow = lane & 31, half hi = lane >> 5; lsw = (lrow >> 1) & 7 is the swizzle term of
 // the lane's row in any block or tile that starts at a multiple of 16 rows.
 #pragma once

@@ -1,8 +1,9 @@
 // attention_probs.hip -- the attention probabilities P[b, h, i, j] of HF's eager attention (CLIPAttention with
 // output_attentions=True, modeling_clip.py eager_attention_forward: softmax(q k^T + causal + padding mask) in fp32),
 // read from the fused qkv activation the q/k/v GEMM writes ([B*S, 3D]: q | k | v, head h at columns head h .. head h + head - 1).
-// The score scale head^-1/2 is already folded into q (engine.hip pack_tower), so the kernel does not apply it.  This unit holds
-// the head-64 kernel; heads of 72 .. 128 run the same body at a padded size from attention_probs_hd.hip.
+// The score scale head^-1/2 is already folded into q (engine.hip pack_tower), so the kernel does not apply it.  Heads of
+// 72 .. 128 run the same body at a padded size: every dot product runs over the head's own columns in ascending order, the arithmetic
+// of the head-64 kernel with another trip count, hence the same bit-for-bit agreement with the summaries (attention_summary.hip).
 //
 // Only plipmi_encode_tower_outputs launches it: the encode paths never form P (attention_mfma.hip keeps an online softmax,
 // qkv_attention.hip never writes qkv).  It is write-bound -- fp32 [B, H, S, S] per layer, 30.7 MB for ViT-B/32 vision at
@@ -30,25 +31,29 @@ __global__ __launch_bounds__(kThreads) void attention_probs_kernel(const T* __re
   probs_block<T, kDh>(qkv, probs, S, H, kDh, causal, key_mask);   // attention_probs_dev.h: the body, shared with the other head sizes
 }
 
+// heads of 72 .. 128: the body at a padded size DP = 96 (head <= 96) or 128, the head a run-time argument
+template <typename T, int DP>
+__global__ __launch_bounds__(kThreads) void attention_probs_hd_kernel(const T* __restrict__ qkv, float* __restrict__ probs, int S, int H,
+                                                                      int head, int causal, const int64_t* __restrict__ key_mask) {
+  probs_block<T, DP>(qkv, probs, S, H, head, causal, key_mask);
+}
+
 }  // namespace
 
 hipError_t launch_attention_probs(const void* qkv, float* probs, int dtype, int B, int S, int H, int head, int causal,
                                   const int64_t* key_mask, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   if (S <= 0 || S > 1024 || H <= 0 || !qkv || !probs || !attention_head_ok(head)) return hipErrorInvalidValue;
-  if (head != kDh) return launch_attention_probs_hd(qkv, probs, dtype, B, S, H, head, causal, key_mask, s);
-  const size_t lds = probs_lds_bytes(S, kDh);    // <= 16 x 1088 x 4 = 68 KiB (S = 1024)
-  const dim3 grid((S + kRows - 1) / kRows, H, B), block(kThreads);
   if (dtype != 0 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  const dim3 grid((S + kRows - 1) / kRows, H, B);
   return with_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
-    if (lds > 64 * 1024) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_probs_kernel<T>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(attention_probs_kernel<T>, grid, block, lds, s, (const T*)qkv, probs, S, H, causal, key_mask);
-    return hipGetLastError();
+    return with_pad(attention_head_pad(head), [&](auto pad) {
+      constexpr int DP = decltype(pad)::value;
+      const size_t lds = probs_lds_bytes(S, DP);    // <= 16 x 1088 x 4 = 68 KiB at head 64 (S = 1024)
+      if constexpr (DP == kDh) return launch_with_lds(&attention_probs_kernel<T>, grid, lds, s, qkv, probs, S, H, causal, key_mask);
+      else return launch_with_lds(&attention_probs_hd_kernel<T, DP>, grid, lds, s, qkv, probs, S, H, head, causal, key_mask);
+    });
   });
 }
 

@@ -4,9 +4,9 @@
 // whatever the tile shape and however its (row, key) pairs are dealt to the lanes: kernels built from these functions produce the
 // same bits for the same (row, key).
 // Head size: the functions take DP, the columns a staged q row has in LDS, and `head`, the columns that exist.  DP = kDh is the
-// head of 64 with every bound a compile-time constant (the kernels of attention_probs.hip / attention_summary.hip); the padded
-// sizes 96 and 128 carry heads of 72 .. 128 (attention_probs_hd.hip): the dot product then runs over `head` columns, so no
-// column past the head is read from memory, and the q row's padding is written as zeros.
+// head of 64 with every bound a compile-time constant; the padded sizes 96 and 128 carry heads of 72 .. 128 (the _hd kernels of
+// attention_probs.hip / attention_summary.hip): the dot product then runs over `head` columns, so no column past the head is read
+// from memory, and the q row's padding is written as zeros.
 #pragma once
 #include "kernels.h"
 
@@ -104,8 +104,8 @@ __device__ __forceinline__ void softmax_row_in_place(float* sr, int S, int lane,
 }
 
 // ---- the kernels' bodies, written once for every head size: attention_probs.hip / attention_summary.hip wrap them at DP = kDh
-// (their kernels are the instructions they were before the head became a parameter: profiles/head_dim_isa_diff.txt),
-// attention_probs_hd.hip at the padded sizes.  Dynamic LDS as each states; what they compute: the kernels' own comments.
+// (their kernels are the instructions they were before the head became a parameter: profiles/head_dim_isa_diff.txt) and, in the
+// _hd kernels beside those, at the padded sizes.  Dynamic LDS as each states; what they compute: the kernels' own comments.
 // (The rollout step's body is attention_rollout_body.inc, included as text: as a function it came out as other instructions.)
 
 // grid (row blocks, H, B); LDS: qs [kRows][DP], sc [kRows][S]
@@ -160,14 +160,19 @@ __device__ __forceinline__ void pooled_rows_block(const T* qkv, const int* row_i
   }
 }
 
-// host side: the dynamic LDS of the three bodies at DP staged columns, and the attribute a launch past 64 KB needs
+// host side: the dynamic LDS of the three bodies at DP staged columns, and the launch of one of their kernels (kThreads lanes per
+// workgroup) with the attribute that dynamic LDS past 64 KB needs
 inline size_t probs_lds_bytes(int S, int DP) { return (size_t)kRows * (DP + S) * sizeof(float); }
 inline size_t pooled_rows_lds_bytes(int S, int DP) { return (size_t)(DP + S) * sizeof(float); }
 inline size_t rollout_lds_bytes(int S, int DP) { return (size_t)kRows * (DP + S + ((S + 3) & ~3)) * sizeof(float); }
-template <typename K>
-inline hipError_t allow_lds(K kernel, size_t lds) {
-  if (lds <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+template <typename... P, typename... A>
+inline hipError_t launch_with_lds(void (*kernel)(P...), dim3 grid, size_t lds, hipStream_t s, A... args) {
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), lds, s, static_cast<P>(args)...);
+  return hipGetLastError();
 }
 
 }  // namespace probs_dev

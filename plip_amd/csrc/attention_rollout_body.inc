@@ -1,5 +1,5 @@
 // attention_rollout_body.inc -- the BODY of the rollout step kernel, included between the braces of a __global__ function
-// (attention_summary.hip: head 64; attention_probs_hd.hip: the padded sizes that carry heads of 72 .. 128).  Text, not a function: as
+// (both in attention_summary.hip: head 64, and the padded sizes that carry heads of 72 .. 128).  Text, not a function: as
 // an inlined function template the head-64 kernels came out with other instructions than before the head became a parameter (the
 // same arithmetic); included as text they are the same instructions (profiles/head_dim_isa_diff.txt).  The including kernel provides
 //   T, RPL               the element type of qkv; tile rows per lane in the score phase and in the product (score_tile)

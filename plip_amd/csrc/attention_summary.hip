@@ -17,7 +17,7 @@
 //                           With row_idx / pooled_out it also stores the pooled query row of every head on its way (the tile that
 //                           holds row rows[b] forms it anyway): the walk then needs no attention_pooled_rows launch.
 //   attention_rollout_row   out [B, S] = row rows[b] of R [B, S, S].
-// This unit holds the head-64 kernels; heads of 72 .. 128 run the same bodies at a padded size from attention_probs_hd.hip.
+// Heads of 72 .. 128 run the same bodies at a padded size (the _hd kernels below).
 // All stores are ordinary vector stores; nothing here uses inline assembly.
 #include "dispatch.h"
 #include "attention_probs_dev.h"
@@ -43,7 +43,24 @@ __global__ __launch_bounds__(kThreads) void attention_rollout_step_kernel(const 
                                                                           const int64_t* __restrict__ key_mask,
                                                                           const int* __restrict__ row_idx, float* __restrict__ pooled_out) {
   constexpr int DP = kDh, head = kDh;
-#include "attention_rollout_body.inc"   // the body, shared with the other head sizes (attention_probs_hd.hip)
+#include "attention_rollout_body.inc"
+}
+
+// heads of 72 .. 128: the two bodies at a padded size DP = 96 (head <= 96) or 128, the head a run-time argument
+template <typename T, int DP>
+__global__ __launch_bounds__(kThreads) void attention_pooled_rows_hd_kernel(const T* __restrict__ qkv, const int* __restrict__ row_idx,
+                                                                            float* __restrict__ out, int S, int H, int head, int causal,
+                                                                            const int64_t* __restrict__ key_mask) {
+  pooled_rows_block<T, DP>(qkv, row_idx, out, S, H, head, causal, key_mask);
+}
+
+template <typename T, int RPL, int DP>
+__global__ __launch_bounds__(kThreads) void attention_rollout_step_hd_kernel(const T* __restrict__ qkv, const float* __restrict__ R_in,
+                                                                             float* __restrict__ R_out, int S, int H, int head, int causal,
+                                                                             const int64_t* __restrict__ key_mask,
+                                                                             const int* __restrict__ row_idx,
+                                                                             float* __restrict__ pooled_out) {
+#include "attention_rollout_body.inc"
 }
 
 __global__ __launch_bounds__(256) void attention_rollout_row_kernel(const float* __restrict__ R, const int* __restrict__ row_idx,
@@ -54,31 +71,16 @@ __global__ __launch_bounds__(256) void attention_rollout_row_kernel(const float*
   for (int j = threadIdx.x; j < S; j += 256) out[(size_t)b * S + j] = src[j];
 }
 
-template <typename T>
-hipError_t pooled_rows(const void* qkv, const int* rows, float* out, int B, int S, int H, int causal, const int64_t* key_mask,
-                       hipStream_t s) {
-  const size_t lds = pooled_rows_lds_bytes(S, kDh);
-  hipLaunchKernelGGL(attention_pooled_rows_kernel<T>, dim3(H, B), dim3(kThreads), lds, s, (const T*)qkv, rows, out, S, H, causal, key_mask);
-  return hipGetLastError();
-}
-
-template <typename T, int RPL>
-hipError_t rollout_step_rpl(const void* qkv, const float* R_in, float* R_out, int B, int S, int H, int causal, const int64_t* key_mask,
-                            const int* rows, float* pooled_out, hipStream_t s) {
-  const size_t lds = rollout_lds_bytes(S, kDh);
-  const hipError_t e = allow_lds(&attention_rollout_step_kernel<T, RPL>, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((attention_rollout_step_kernel<T, RPL>), dim3((S + kRows - 1) / kRows, B), dim3(kThreads), lds, s, (const T*)qkv,
-                     R_in, R_out, S, H, causal, key_mask, rows, pooled_out);
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t rollout_step(const void* qkv, const float* R_in, float* R_out, int B, int S, int H, int causal, const int64_t* key_mask,
-                        const int* rows, float* pooled_out, hipStream_t s) {
-  if (S <= 64) return rollout_step_rpl<T, 4>(qkv, R_in, R_out, B, S, H, causal, key_mask, rows, pooled_out, s);
-  if (S <= 128) return rollout_step_rpl<T, 8>(qkv, R_in, R_out, B, S, H, causal, key_mask, rows, pooled_out, s);
-  return rollout_step_rpl<T, 16>(qkv, R_in, R_out, B, S, H, causal, key_mask, rows, pooled_out, s);
+template <typename T, int RPL, int DP>
+hipError_t rollout_step_rpl(const void* qkv, const float* R_in, float* R_out, int B, int S, int H, int head, int causal,
+                            const int64_t* key_mask, const int* rows, float* pooled_out, hipStream_t s) {
+  const size_t lds = rollout_lds_bytes(S, DP);
+  const dim3 grid((S + kRows - 1) / kRows, B);
+  if constexpr (DP == kDh)
+    return launch_with_lds(&attention_rollout_step_kernel<T, RPL>, grid, lds, s, qkv, R_in, R_out, S, H, causal, key_mask, rows, pooled_out);
+  else
+    return launch_with_lds(&attention_rollout_step_hd_kernel<T, RPL, DP>, grid, lds, s, qkv, R_in, R_out, S, H, head, causal, key_mask, rows,
+                           pooled_out);
 }
 
 }  // namespace
@@ -90,8 +92,15 @@ hipError_t launch_attention_pooled_rows(const void* qkv, const int* rows, float*
   if (B <= 0) return hipSuccess;
   if (S <= 0 || S > 1024 || H <= 0 || B > 65535 || !qkv || !rows || !out || !attention_head_ok(head)) return hipErrorInvalidValue;
   if (dtype != 0 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
-  if (head != kDh) return launch_attention_pooled_rows_hd(qkv, rows, out, dtype, B, S, H, head, causal, key_mask, s);
-  return with_dtype(dtype, [&](auto tag) { return pooled_rows<decltype(tag)>(qkv, rows, out, B, S, H, causal, key_mask, s); });
+  return with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return with_pad(attention_head_pad(head), [&](auto pad) {
+      constexpr int DP = decltype(pad)::value;
+      const size_t lds = pooled_rows_lds_bytes(S, DP);
+      if constexpr (DP == kDh) return launch_with_lds(&attention_pooled_rows_kernel<T>, dim3(H, B), lds, s, qkv, rows, out, S, H, causal, key_mask);
+      else return launch_with_lds(&attention_pooled_rows_hd_kernel<T, DP>, dim3(H, B), lds, s, qkv, rows, out, S, H, head, causal, key_mask);
+    });
+  });
 }
 
 hipError_t launch_attention_rollout_step(const void* qkv, const float* R_in, float* R_out, int dtype, int B, int S, int H, int head,
@@ -100,9 +109,14 @@ hipError_t launch_attention_rollout_step(const void* qkv, const float* R_in, flo
   if (S <= 0 || S > 1024 || H <= 0 || B > 65535 || !qkv || !R_out || R_in == R_out || (pooled_out && !rows) || !attention_head_ok(head))
     return hipErrorInvalidValue;
   if (dtype != 0 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
-  if (head != kDh) return launch_attention_rollout_step_hd(qkv, R_in, R_out, dtype, B, S, H, head, causal, key_mask, s, rows, pooled_out);
   return with_dtype(dtype, [&](auto tag) {
-    return rollout_step<decltype(tag)>(qkv, R_in, R_out, B, S, H, causal, key_mask, rows, pooled_out, s);
+    using T = decltype(tag);
+    return with_pad(attention_head_pad(head), [&](auto pad) {
+      constexpr int DP = decltype(pad)::value;
+      if (S <= 64) return rollout_step_rpl<T, 4, DP>(qkv, R_in, R_out, B, S, H, head, causal, key_mask, rows, pooled_out, s);
+      if (S <= 128) return rollout_step_rpl<T, 8, DP>(qkv, R_in, R_out, B, S, H, head, causal, key_mask, rows, pooled_out, s);
+      return rollout_step_rpl<T, 16, DP>(qkv, R_in, R_out, B, S, H, head, causal, key_mask, rows, pooled_out, s);
+    });
   });
 }
 

@@ -1,5 +1,5 @@
 // attention_valu_body.inc -- the BODY of the exact-fp32 VALU attention kernel, included between the braces of a __global__ function
-// (attention.hip: head 64, the kernel it has always been; attention_valu_hd.hip: the padded sizes that carry heads of 72 .. 128).
+// (both in attention.hip: head 64, the kernel it has always been, and the padded sizes that carry heads of 72 .. 128).
 // Text, not a function: as an inlined function template the head-64 kernels came out with other operand orders and register
 // assignments than before the head became a parameter (the same arithmetic, other instructions); included as text they are the
 // same instructions (profiles/head_dim_isa_diff.txt).  The including kernel provides

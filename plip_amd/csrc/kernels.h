@@ -124,21 +124,16 @@ hipError_t launch_scale_copy(const float* src, float* dst, int n, float scale, h
 // with qkv_attention.hip, are in attention_mfma_dev.h) =====
 // Multi-head attention over the fused qkv buffer [B*S, 3*D] (D = H * head; q | k | v, head h at columns h*head..), the
 // 1/sqrt(head) scale already folded into q.  out [B*S, D].  causal: key j <= query i.  key_mask: int64 [B,S] or nullptr.
-//   head  64, or 72 .. 128 in steps of 8 (attention_head_ok).  64 runs the kernels of attention.hip / attention_mfma.hip; the others
-//         run attention_valu_hd.hip / attention_mfma_hd.hip at the padded size attention_head_pad(head) -- columns past the head are
-//         zeros in LDS, never read from memory and never stored
-//   impl 0 = exact fp32 VALU kernel (any dtype), 1 = MFMA kernel (dtype bf16 or f16)
+//   head  64, or 72 .. 128 in steps of 8 (attention_head_ok).  The kernels are instantiated at attention_head_pad(head) columns: 64,
+//         or a padded size whose columns past the head are zeros in LDS, never read from memory and never stored
+//   impl 0 = exact fp32 VALU kernel (any dtype, S <= 1024), 1 = MFMA kernel (dtype bf16 or f16; heads other than 64: one chunked
+//   kernel for every S)
 //   cu (impl 1, S <= 128, head 64): packed rows -- sample b owns rows cu[b] .. cu[b+1]-1 of qkv / out (its first cu[b+1]-cu[b]
 //   positions; the rest of its S positions do not exist); key_mask keeps its [B, S] layout
 inline bool attention_head_ok(int head) { return head >= 64 && head <= 128 && head % 8 == 0; }
 inline int attention_head_pad(int head) { return head == 64 ? 64 : head <= 96 ? 96 : 128; }
 hipError_t launch_attention(const void* qkv, void* out, int dtype, int B, int S, int H, int head, int causal,
                             const int64_t* key_mask, int impl, hipStream_t s, const int* cu = nullptr);
-// the kernels of the other head sizes (launch_attention dispatches to them; head != 64, checked by the caller)
-hipError_t launch_attention_valu_hd(const void* qkv, void* out, int dtype, int B, int S, int H, int head, int causal,
-                                    const int64_t* key_mask, hipStream_t s);
-hipError_t launch_attention_mfma_hd(const void* qkv, void* out, int dtype, int B, int S, int H, int head, int causal,
-                                    const int64_t* key_mask, hipStream_t s);
 
 // ===== qkv_attention.hip =====
 // The text tower's LayerNorm-folded q/k/v projection with the attention in its epilogue (qkv_attention.hip): one launch, no
@@ -154,12 +149,9 @@ hipError_t launch_qkv_attention(int dtype, const void* A, const void* W, const f
 // ===== attention_probs.hip =====
 // Attention probabilities of HF's eager attention (attention_probs.hip, plipmi_encode_tower_outputs only): fp32
 // probs [B, H, S, S] = softmax(q k^T + mask) from the same qkv buffer (dtype 0 fp32, 1 bf16, 2 f16), the same causal / key_mask
-// rules; masked entries exactly 0, a row with no live key all 0.  S <= 1024.  head as launch_attention (other than 64:
-// attention_probs_hd.hip, which also holds the summaries' kernels for those heads).
+// rules; masked entries exactly 0, a row with no live key all 0.  S <= 1024.  head as launch_attention.
 hipError_t launch_attention_probs(const void* qkv, float* probs, int dtype, int B, int S, int H, int head, int causal,
                                   const int64_t* key_mask, hipStream_t s);
-hipError_t launch_attention_probs_hd(const void* qkv, float* probs, int dtype, int B, int S, int H, int head, int causal,
-                                     const int64_t* key_mask, hipStream_t s);
 
 // ===== attention_summary.hip =====
 // Attention summaries (attention_summary.hip, plipmi_encode_attention_summary only), from the same qkv buffer and under the same
@@ -175,10 +167,6 @@ hipError_t launch_attention_pooled_rows(const void* qkv, const int* rows, float*
 hipError_t launch_attention_rollout_step(const void* qkv, const float* R_in, float* R_out, int dtype, int B, int S, int H, int head,
                                          int causal, const int64_t* key_mask, hipStream_t s, const int* rows = nullptr,
                                          float* pooled_out = nullptr);
-hipError_t launch_attention_pooled_rows_hd(const void* qkv, const int* rows, float* out, int dtype, int B, int S, int H, int head,
-                                           int causal, const int64_t* key_mask, hipStream_t s);
-hipError_t launch_attention_rollout_step_hd(const void* qkv, const float* R_in, float* R_out, int dtype, int B, int S, int H, int head,
-                                            int causal, const int64_t* key_mask, hipStream_t s, const int* rows, float* pooled_out);
 hipError_t launch_attention_rollout_row(const float* R, const int* rows, float* out, int B, int S, hipStream_t s);
 
 // ===== token_scores.hip =====

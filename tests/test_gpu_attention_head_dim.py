@@ -1,5 +1,6 @@
 """Kernel-level parity of the attention kernels at head sizes other than 64 (include/plipmi_test.h ``plipmi_attention_hd`` and the three
-``_hd`` entries of the probabilities and their summaries; csrc/attention_valu_hd.hip, attention_mfma_hd.hip, attention_probs_hd.hip).
+``_hd`` entries of the probabilities and their summaries; the padded-head kernels of csrc/attention.hip, attention_mfma.hip,
+attention_probs.hip and attention_summary.hip).
 
 The reference is the fp64 softmax(Q K^T) V of tests/test_gpu_attention.py with the head size as a parameter, q pre-scaled by
 head^-0.5 * 3, and that file's tolerances unchanged: they come from the rounding of the outputs (and of P as an MFMA operand), not from
@@ -120,6 +121,30 @@ def test_head_64_through_the_new_entry_is_the_old_kernel():
         qkv = torch.randn(2 * S, 3 * H * 64, generator=g).to(DEV).to(torch.bfloat16)
         for impl in (0, 1):
             assert torch.equal(attention(qkv, 2, S, H, impl=impl, head_dim=64), attention(qkv, 2, S, H, impl=impl))
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+@pytest.mark.parametrize("S,causal,lens", [(129, False, None), (300, True, (300, 141))], ids=["S129_plain", "S300_causal_mask"])
+def test_padded_flash_kernel_is_the_head_64_chunked_kernel_on_a_zero_padded_head(S, causal, lens, dtype):
+    """The two chunked MFMA kernels take one online-softmax step (csrc/attention_flash_step.inc) and perform the same operations in the
+    same order per query.  A head-72 problem whose q and k columns 64 .. 71 are zeros is the head-64 problem: the extra k-step adds exact
+    zeros to every score, and output tiles 0 and 1 read the same V columns (v columns 64 .. 71 are arbitrary: they only reach output
+    columns 64 ..).  So columns 0 .. 63 of every head must be the head-64 kernel's output BIT FOR BIT.  S > 128: at or below it head 64
+    takes the single-pass kernel, which is other arithmetic."""
+    from plip_amd.kernel_entries import attention
+    B = 2
+    g = torch.Generator().manual_seed(64 * S)
+    x64 = torch.randn(B * S, 3, H, 64, generator=g)
+    x64[:, 0] *= 64 ** -0.5 * 3.0                       # q pre-scaled; x3 sharpens the softmax
+    x72 = torch.zeros(B * S, 3, H, 72)
+    x72[..., :64] = x64
+    x72[:, 2, :, 64:] = torch.randn(B * S, H, 8, generator=g)
+    mask = None if lens is None else (torch.arange(S)[None, :] < torch.tensor(lens)[:, None]).long().to(DEV)
+    o64 = attention(x64.reshape(B * S, 3 * H * 64).to(dtype).to(DEV), B, S, H, causal, mask, impl=1, head_dim=64)
+    o72 = attention(x72.reshape(B * S, 3 * H * 72).to(dtype).to(DEV), B, S, H, causal, mask, impl=1, head_dim=72)
+    torch.cuda.synchronize()
+    assert torch.isfinite(o64).all()
+    assert torch.equal(o72.reshape(B * S, H, 72)[..., :64], o64.reshape(B * S, H, 64))
 
 
 @pytest.mark.parametrize("head", [32, 56, 100, 136, 192])

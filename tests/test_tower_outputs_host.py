@@ -86,8 +86,10 @@ def test_probability_kernel_resources(tmp_path):
     assert r.returncode == 0, r.stderr
     kernels = re.findall(r"Function Name: (\S*attention_probs_kernel\S*)", r.stderr)
     assert len(kernels) == 3, kernels      # fp32, bf16, f16
+    padded = re.findall(r"Function Name: (\S*attention_probs_hd_kernel\S*)", r.stderr)
+    assert len(padded) == 6, padded        # x the padded head sizes 96 and 128: the same unit, the same rules
     for key in ("ScratchSize \\[bytes/lane\\]", "VGPRs Spill", "SGPRs Spill", "LDS Size \\[bytes/block\\]"):
         vals = re.findall(r"%s: (\d+)" % key, r.stderr)
-        assert len(vals) == 3 and all(v == "0" for v in vals), (key, vals)
+        assert len(vals) == 9 and all(v == "0" for v in vals), (key, vals)
     vgprs = [int(v) for v in re.findall(r"\bVGPRs: (\d+)", r.stderr)]
-    assert len(vgprs) == 3 and max(vgprs) <= 128, vgprs
+    assert len(vgprs) == 9 and max(vgprs) <= 128, vgprs
