@@ -519,6 +519,54 @@ int plipmi_probe_predict(plipmi_handle h, const float* X, int N, int D, const fl
 int plipmi_softmax_fit(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int C, const float* class_w, float alpha,
                        int max_iter, float gtol, float* WB_inout, plipmi_probe_info* info_out, void* stream);
 
+/* ---- k-means on cached embeddings ----------------------------------------------
+ * (Additive, like the entries above it: the version number and every existing entry are unchanged; a caller probes for the symbols.)
+ * Lloyd's algorithm over X fp32 [N, D] (device, 16-byte aligned, D % 4 == 0, 4 <= D <= 1024, finite values) with
+ * 1 <= K <= min(N, PLIPMI_KMEANS_MAX_K) centres fp32 [K, D] (16-byte aligned too).  Both metrics are one score with a per-centre bias,
+ *   s_ik = x_i . c_k + h_k,      label_i = the FIRST arg-max over k (ties go to the lower k):
+ *   PLIPMI_KMEANS_EUCLIDEAN  h_k = -1/2 |c_k|^2, d_i = max(0, |x_i|^2 - 2 s_i), new centre = the mean of its members
+ *                            (scikit-learn's KMeans(algorithm="lloyd"))
+ *   PLIPMI_KMEANS_COSINE     spherical k-means: rows are used as given (the caller passes unit rows), h_k = 0, d_i = max(0, 1 - s_i),
+ *                            new centre = the members' sum divided by its norm; a zero sum counts as an empty cluster
+ * inertia = sum_i d_i.  csrc/kmeans.hip: the scores are exact-fp32 MFMA products, no N x K buffer exists, every floating-point
+ * reduction has a fixed order and there are no floating-point atomics -- the same inputs give the same bits on every run.
+ * Whatever the input, a label written is in [0, K).  Scratch is a workspace of the handle's own, grown on first use.
+ * Anything outside the limits above (a null pointer, an unknown metric, D % 4, D outside 4 .. 1024, K outside 1 .. min(N, 4096), a
+ * misaligned X) is PLIPMI_ERR_INVALID with a message that names the limit, before any launch.
+ *
+ * plipmi_kmeans_seed: plain k-means++ D^2 sampling (NOT scikit-learn's greedy variant), entirely on the device, no synchronisation,
+ * from K uniforms in [0, 1) on the HOST.  Pick 0 is row floor(u_0 N).  Step t: mind_i is lowered to the distance d to the centre
+ * just picked, mind is summed in float64 in a fixed order, and the pick is the first row whose float64 prefix sum over ascending i
+ * exceeds u_t * total (total == 0: the lowest row not yet picked).  centers[t] = X[picks[t]] bit for bit; picks (device int32 [K])
+ * may be NULL.
+ * plipmi_kmeans_assign: labels int32 [N] and scores fp32 [N] (s_i,label; may be NULL) for the given centres.  Enqueues only.
+ * plipmi_kmeans_fit: Lloyd's loop on the host from centers_inout, which it overwrites.  It SYNCHRONISES the stream once per
+ * iteration (like plipmi_probe_fit) and reads back a few bytes: the number of changed labels, the number of empty clusters and the
+ * centre shift sum_k |delta c_k|^2.  It stops when no label changed or when the shift is <= tol_abs (info.converged = 1), or after
+ * max_iter iterations (converged = 0, still PLIPMI_OK: reaching max_iter is normal for k-means).  Empty clusters: in ascending k,
+ * an empty cluster takes as its centre the row with the largest d_i not yet taken in this iteration (ties: the lower row); each move
+ * counts in info.relocations, and an iteration that moved a centre does not stop the loop (the rare path: it copies the scores to
+ * the host and synchronises once more).  The shift counts the clusters that have members.  On return labels, scores, counts [K],
+ * reps [K] (the member with the largest score, ties to the lower row; scores / counts / reps may be NULL) and info.inertia all
+ * belong to the returned centres. */
+#define PLIPMI_KMEANS_MAX_K 4096
+enum { PLIPMI_KMEANS_EUCLIDEAN = 0, PLIPMI_KMEANS_COSINE = 1 };
+typedef struct plipmi_kmeans_info {
+  int32_t iterations;    /* Lloyd iterations run (scikit-learn's n_iter_) */
+  int32_t converged;     /* 1: no label changed, or the shift fell to tol_abs; 0: stopped at max_iter */
+  int32_t relocations;   /* empty clusters given a new centre, over the whole fit */
+  int32_t reserved;
+  double  inertia;       /* sum_i d_i at the returned centres */
+  double  center_shift;  /* sum_k |delta c_k|^2 of the last iteration */
+} plipmi_kmeans_info;
+int plipmi_kmeans_seed(plipmi_handle h, const float* X, int N, int D, int K, int metric, const double* u_host, float* centers,
+                       int32_t* picks, void* stream);
+int plipmi_kmeans_assign(plipmi_handle h, const float* X, int N, int D, const float* centers, int K, int metric, int32_t* labels,
+                         float* scores, void* stream);
+int plipmi_kmeans_fit(plipmi_handle h, const float* X, int N, int D, int K, int metric, int max_iter, double tol_abs,
+                      float* centers_inout, int32_t* labels, float* scores, int32_t* counts, int32_t* reps, plipmi_kmeans_info* info,
+                      void* stream);
+
 /* ---- measurement ------------------------------------------------------------
  * (kernel-level test entries and A/B hooks live in plipmi_test.h: same library, not part of the product interface) */
 /* Per-kernel timing with HIP events recorded on the launch stream.  While

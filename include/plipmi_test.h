@@ -235,6 +235,14 @@ int plipmi_token_scores(const float* E, int M, int P, const float* T, int C, flo
 int plipmi_softmax_loss_grad(plipmi_handle h, const float* X, int N, int D, const int32_t* y, int C, const float* class_w, float alpha,
                              const float* WB, double* loss_out, float* grad_out, void* stream);
 
+/* The update step of k-means alone (csrc/kmeans.hip; limits as plipmi_kmeans_fit in plipmi.h), for tests/test_gpu_kmeans.py: from
+ * labels int32 [N] and scores fp32 [N] to sums fp32 [K, D], counts int32 [K], reps int32 [K] (the member with the largest score, ties to
+ * the lower row, -1 for an empty cluster) and inertia double [1] = sum_i d_i in the given metric (the argument the distance needs: d_i
+ * is |x_i|^2 - 2 s_i or 1 - s_i).  A row whose label is outside [0, K) belongs to no cluster and adds nothing.  Device buffers;
+ * deterministic; enqueues only. */
+int plipmi_kmeans_update(plipmi_handle h, const float* X, int N, int D, const int32_t* labels, const float* scores, int K, int metric,
+                         float* sums, int32_t* counts, int32_t* reps, double* inertia, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

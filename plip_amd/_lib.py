@@ -75,6 +75,15 @@ class ProbeInfo(C.Structure):
                 ("grad_norm", C.c_double), ("loss", C.c_double * PROBE_MAX_K)]
 
 
+KMEANS_MAX_K = 4096    # include/plipmi.h PLIPMI_KMEANS_MAX_K
+KMEANS_METRICS = {"euclidean": 0, "cosine": 1}   # PLIPMI_KMEANS_EUCLIDEAN / PLIPMI_KMEANS_COSINE
+
+
+class KMeansInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("relocations", C.c_int32), ("reserved", C.c_int32),
+                ("inertia", C.c_double), ("center_shift", C.c_double)]
+
+
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 # kernel-level test entries and A/B hooks (include/plipmi_test.h): tests/, tools/ and bench.py's side fields only
 TEST_SYMBOLS = {
@@ -119,6 +128,7 @@ TEST_SYMBOLS = {
     "plipmi_attention_rollout_step_hd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "plipmi_token_scores": (_i, [_vp, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
     "plipmi_softmax_loss_grad": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp]),
+    "plipmi_kmeans_update": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 # every symbol include/plipmi.h declares (the product interface): (restype, argtypes)
 SYMBOLS = {
@@ -155,6 +165,9 @@ SYMBOLS = {
     "plipmi_probe_fit": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _f, _i, _f, _vp, C.POINTER(ProbeInfo), _vp]),
     "plipmi_probe_predict": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "plipmi_softmax_fit": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _f, _i, _f, _vp, C.POINTER(ProbeInfo), _vp]),
+    "plipmi_kmeans_seed": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_double), _vp, _vp, _vp]),
+    "plipmi_kmeans_assign": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "plipmi_kmeans_fit": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, C.POINTER(KMeansInfo), _vp]),
     "plipmi_profile_enable": (_i, [_vp, _i]),
     "plipmi_profile_read": (_i, [_vp, C.POINTER(KernelStat), _i, C.POINTER(_i)]),
 }

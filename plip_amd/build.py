@@ -31,6 +31,11 @@ SOURCES = ["engine.hip", "towers.hip", "heads.hip", "test_entries.hip", "gemm.hi
            "augment.hip",
            # the slide-region entries and their kernels (tissue count, compaction, tile gather), likewise
            "region.hip"]
+# Units added since, compiled and linked behind SOURCES in this order (SOURCES itself is closed: tests/test_region_host.py and
+# tests/test_augment_host.py pin its last entries, and the stand-alone sanitizer programs of tests/ link exactly its objects; a unit here
+# must therefore be one that no unit of SOURCES calls into).
+# k-means on cached embeddings (assignment, update, finalise, seeding) and its entries: behind everything that existed, like the units above
+LATER_SOURCES = ["kmeans.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-Wno-unused-value"]
 
@@ -83,7 +88,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     hdr_digest = _digest(headers)
     jobs = []
     objs = []
-    for src in SOURCES:
+    for src in SOURCES + LATER_SOURCES:
         obj = os.path.join(BUILD, src.replace(".hip", ".o"))
         stamp = obj + ".sha"
         want = _digest([os.path.join(CSRC, src)]) + hdr_digest

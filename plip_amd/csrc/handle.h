@@ -285,6 +285,10 @@ struct plipmi_engine {
   // linear-probe scratch (plipmi_probe_fit / _predict / _loss_grad): device partials + results, and a pinned host mirror of the
   // trial point, gradient and losses.  Allocations of their own, grown on demand: never part of the tower workspace.
   plipmi::Buffer probe_ws, probe_host{plipmi::Buffer::kPinned};
+  // k-means scratch (plipmi_kmeans_seed / _assign / _fit / _update, kmeans.hip): row norms, centre biases, the sorted row order, the
+  // per-chunk partial sums and the few bytes a fit reads back; a pinned host mirror for those bytes and for the rare empty-cluster
+  // path.  Allocations of their own, grown on demand: never part of the tower workspace.
+  plipmi::Buffer kmeans_ws, kmeans_host{plipmi::Buffer::kPinned};
   plipmi::Profile prof;
 
   explicit plipmi_engine(std::shared_ptr<const plipmi::Model> m) : model(std::move(m)) {

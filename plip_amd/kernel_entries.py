@@ -283,6 +283,24 @@ def softmax_loss_grad(engine, x: torch.Tensor, y: torch.Tensor, wb: torch.Tensor
     return loss, grad
 
 
+def kmeans_update(engine, x: torch.Tensor, labels: torch.Tensor, scores: torch.Tensor, sums: torch.Tensor, counts: torch.Tensor,
+                  reps: torch.Tensor, inertia: torch.Tensor, metric: int, n: Optional[int] = None, k: Optional[int] = None) -> None:
+    """The update step of k-means (include/plipmi_test.h ``plipmi_kmeans_update``) INTO the caller's buffers, so a test can fill them with
+    sentinels and hang guard rows behind them: x fp32 [>= N, D], labels int32 [>= N], scores fp32 [>= N] -> sums fp32 [>= K, D], counts /
+    reps int32 [>= K], inertia double [>= 1].  ``n`` / ``k`` default to the leading sizes of x / sums.  metric: 0 euclidean, 1 cosine."""
+    lib = _lib.load()
+    for t, dt in ((x, torch.float32), (labels, torch.int32), (scores, torch.float32), (sums, torch.float32), (counts, torch.int32),
+                  (reps, torch.int32), (inertia, torch.float64)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous()
+    N = x.shape[0] if n is None else int(n)
+    K = sums.shape[0] if k is None else int(k)
+    D = x.shape[1]
+    assert sums.shape[1] == D
+    with torch.cuda.device(x.device):
+        _lib.check(lib.plipmi_kmeans_update(engine._h, _ptr(x), N, D, _ptr(labels), _ptr(scores), K, int(metric), _ptr(sums), _ptr(counts),
+                                            _ptr(reps), _ptr(inertia), _stream_ptr(x.device)), "plipmi_kmeans_update")
+
+
 # ---- the kernels around the GEMMs (include/plipmi_test.h, tests/test_gpu_small_kernels.py) ---------------------------------------------
 def _f32(*ts):
     for t in ts:

@@ -89,3 +89,20 @@ def token_similarity_bytes(B: int, S: int, D: int, P: int, C: int, token_embeds:
     return {"similarity": 4 * B * S * C,
             "token_embeds": 4 * B * S * P if token_embeds else 0,
             "scratch": ln + (0 if token_embeds else 4 * B * S * P)}
+
+
+@dataclass
+class KMeansResult:
+    """``plip_amd.kmeans.kmeans_fit`` (include/plipmi.h plipmi_kmeans_fit): device tensors and Python scalars.  ``centers`` fp32 [K,D];
+    ``labels`` int32 [N]; ``scores`` fp32 [N], each row's ``x . c + h`` at its own centre; ``counts`` int32 [K]; ``representatives`` int32
+    [K], the member of each cluster with the largest score (-1 for an empty cluster); ``inertia``; ``n_iter``; ``converged``;
+    ``relocations``, the empty clusters that were given a new centre.  Everything belongs to the returned ``centers``."""
+    centers: torch.Tensor
+    labels: torch.Tensor
+    scores: torch.Tensor
+    counts: torch.Tensor
+    representatives: torch.Tensor
+    inertia: float
+    n_iter: int
+    converged: bool
+    relocations: int

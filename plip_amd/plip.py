@@ -197,6 +197,40 @@ class PLIP:
         return encode_region(eng, region, n_px, self.model.config.projection_dim, _CROP, tile_px=tile_px, stride=stride, origin=origin,
                              min_tissue=min_tissue, sat_min=sat_min, luma_min=luma_min, luma_max=luma_max, band_rows=band_rows)
 
+    def cluster_embeddings(self, embeddings, n_clusters: int, metric: str = "cosine", **kw):
+        """(extension) K-means on cached embeddings [N,P] (numpy or torch, host or device) on the GPU (kmeans.py ``kmeans_fit``, whose
+        keyword arguments ``init``, ``n_init``, ``max_iter``, ``tol``, ``seed`` pass through).  ``metric="cosine"`` (spherical k-means)
+        L2-normalises a copy of the rows first; "euclidean" uses them as given.  Returns an ``outputs.KMeansResult``."""
+        from .kmeans import _metric, _x_on_device, kmeans_fit
+        _metric(metric)
+        eng = self.model.engine
+        x = embeddings
+        if metric == "cosine":
+            with torch.cuda.device(eng.device):
+                x = _x_on_device(eng, embeddings, "cluster_embeddings")
+                x = eng.l2_normalize_(x.clone())
+        return kmeans_fit(eng, x, n_clusters, metric=metric, **kw)
+
+    def region_mosaic(self, region, n_clusters: int, seed: int = 0, **encode_region_kwargs):
+        """(extension) The "mosaic" of a slide region: ``encode_region`` (its keyword arguments pass through), spherical k-means on the
+        L2-normalised tile embeddings, one representative tile per cluster.  Fewer kept tiles than ``n_clusters`` lower K to the tile
+        count; a region without tissue returns empty arrays and launches nothing.  Returns a ``region_routes.RegionMosaic``."""
+        from .kmeans import kmeans_fit
+        from .region_routes import RegionMosaic
+        if int(n_clusters) < 1:
+            raise ValueError(f"region_mosaic: need n_clusters >= 1, got {n_clusters}")
+        reg = self.encode_region(region, **encode_region_kwargs)
+        n_tiles = reg.embeddings.shape[0]
+        if n_tiles == 0:
+            return RegionMosaic(reg, np.zeros((0,), np.int64), np.zeros((0, 2), np.int64), np.zeros((0,), np.int64), np.zeros((0,), np.int32),
+                                np.zeros((0,), np.int32), None)
+        eng = self.model.engine
+        with torch.cuda.device(eng.device):
+            x = eng.l2_normalize_(torch.from_numpy(np.ascontiguousarray(reg.embeddings, dtype=np.float32)).to(eng.device))
+        res = kmeans_fit(eng, x, min(int(n_clusters), n_tiles), metric="cosine", seed=seed)
+        reps = res.representatives.cpu().numpy().astype(np.int64)
+        return RegionMosaic(reg, reps, reg.coords[reps], reg.kept[reps], res.labels.cpu().numpy(), res.counts.cpu().numpy(), res)
+
     def encode_views(self, images, batch_size: int, views: int = 8, transform: str = "d4", seed: int = 0, reduce: Optional[str] = None,
                      return_params: bool = False):
         """(extension) Embeddings of ``views`` augmented views of every tile, the views built on the GPU (augment.py; Pillow-exact

@@ -53,6 +53,20 @@ def _band_rows(region, eng, pitch: int, t: int, s: int, rows: int, band_rows: Op
     return max(1, min(rows if band_rows is None else int(band_rows), fit, rows))
 
 
+@dataclass
+class RegionMosaic:
+    """``PLIP.region_mosaic``: ``region`` = the ``RegionEmbeddings`` of the kept tiles; per cluster, ``representatives`` int64 [K] (the
+    representative tile's index into the kept tiles) and ``rep_coords`` int64 [K,2] = ``region.coords[representatives]`` and ``rep_kept`` int64 [K] = ``region.kept[representatives]``, its
+    flat grid index; ``labels`` int32 [tiles], every kept tile's cluster; ``counts`` int32 [K]; ``result``, the ``outputs.KMeansResult`` (None for a region without tissue)."""
+    region: RegionEmbeddings
+    representatives: np.ndarray
+    rep_coords: np.ndarray
+    rep_kept: np.ndarray
+    labels: np.ndarray
+    counts: np.ndarray
+    result: Optional[object]
+
+
 def encode_region(eng, region, n_px: int, projection_dim: int, crop: str, tile_px: Optional[int] = None, stride: Optional[int] = None,
                   origin=(0, 0), min_tissue: float = 0.5, sat_min: int = 18, luma_min: int = 25, luma_max: int = 235,
                   band_rows: Optional[int] = None) -> RegionEmbeddings:
