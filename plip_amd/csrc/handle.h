@@ -54,6 +54,15 @@ inline bool valid_tower(int tower) { return tower == PLIPMI_VISION || tower == P
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// What every head on cached embeddings asks of X [N, D] fp32 (heads.hip probe_check / softmax_check, kmeans.hip km_check): rows, a width
+// probe_tile.h has a tile for, 16-byte loads.  `who` ("" or "entry: ") goes in front of the message.
+inline int check_embeddings(const char* who, const void* X, int N, int D) {
+  if (N <= 0) return fail(PLIPMI_ERR_INVALID, "%sneed N > 0 rows, got %d", who, N);
+  if (D < 4 || D > 1024 || D % 4) return fail(PLIPMI_ERR_INVALID, "%sembedding width %d unsupported (D %% 4 == 0, 4 <= D <= 1024)", who, D);
+  if (reinterpret_cast<uintptr_t>(X) % 16) return fail(PLIPMI_ERR_INVALID, "%sX must be 16-byte aligned", who);
+  return PLIPMI_OK;
+}
+
 struct Carver {  // two-pass slab carving: pass 1 sizes (base == nullptr), pass 2 hands out pointers
   char* base = nullptr;
   size_t off = 0;

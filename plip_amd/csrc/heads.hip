@@ -1,5 +1,6 @@
 // heads.hip -- what runs on embeddings and images outside the towers: L2 normalisation, logits, top-k and the streaming
-// similarity top-k, the Pillow-exact resize entries, and the linear-probe drivers (probe.hip, probe_softmax.hip, probe_solver.h).
+// similarity top-k, the Pillow-exact resize entries, and the linear-probe drivers (probe.hip, probe_softmax.hip, probe_solver.h): both
+// fits run probe_solve below, K machines of D + 1 variables or one machine of C (D + 1).
 #include <algorithm>
 #include <cmath>
 
@@ -8,6 +9,61 @@
 #include "resize_ragged.h"
 
 using namespace plipmi;
+
+namespace {
+
+struct ProbeSolve { int evals, conv, worst; double gmax; };      // worst: the machine with the largest final gradient, gmax
+
+// The solver loop of both probe fits: `machines` L-BFGS machines (probe_solver.h) of n variables each on WB_inout [machines][n], one
+// loss per machine.  Every pass evaluates all the current trial points in one call, eval(&grad, &loss), which leaves device pointers to
+// fp32 [machines][n] and double [machines]; the trial points travel through WB_inout itself, which ends holding every machine's final
+// point.  Fills info_out (may be nullptr) and *out; a machine that did not converge (out->conv < machines) is the caller's to report.
+template <typename Eval>
+int probe_solve(plipmi_handle h, int machines, int n, int max_iter, float gtol, float* WB_inout, plipmi_probe_info* info_out,
+                hipStream_t s, Eval&& eval, ProbeSolve* out) {
+  const size_t wb_bytes = (size_t)machines * n * 4;
+  RUN(h->probe_host.reserve(2 * align_up(wb_bytes, 256) + align_up((size_t)machines * 8, 256), s));
+  float* wb_h = reinterpret_cast<float*>(h->probe_host.data());
+  float* g_h = reinterpret_cast<float*>(h->probe_host.data() + align_up(wb_bytes, 256));
+  double* l_h = reinterpret_cast<double*>(h->probe_host.data() + 2 * align_up(wb_bytes, 256));
+
+  HIP_TRY(hipMemcpyAsync(wb_h, WB_inout, wb_bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (size_t i = 0; i < (size_t)machines * n; ++i)
+    if (!std::isfinite(wb_h[i])) return fail(PLIPMI_ERR_INVALID, "the starting point WB_inout holds a non-finite value");
+  std::vector<ProbeLbfgs> prob(machines);
+  for (int k = 0; k < machines; ++k) prob[k].init(wb_h + (size_t)k * n, n, max_iter, (double)gtol);
+  *out = ProbeSolve{0, 0, -1, 0.0};
+  for (;;) {
+    for (int k = 0; k < machines; ++k) prob[k].trial(wb_h + (size_t)k * n);
+    HIP_TRY(hipMemcpyAsync(WB_inout, wb_h, wb_bytes, hipMemcpyHostToDevice, s));
+    bool all_done = true;
+    for (int k = 0; k < machines; ++k) all_done = all_done && prob[k].done;
+    if (all_done) break;
+    float* grad; double* loss;
+    RUN(eval(&grad, &loss));
+    HIP_TRY(hipMemcpyAsync(g_h, grad, wb_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(l_h, loss, (size_t)machines * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ++out->evals;
+    for (int k = 0; k < machines; ++k) prob[k].feed(l_h[k], g_h + (size_t)k * n);
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  int iters = 0;
+  for (int k = 0; k < machines; ++k) {
+    iters = std::max(iters, prob[k].iters);
+    out->conv += prob[k].converged ? 1 : 0;
+    if (prob[k].gnorm >= out->gmax) { out->gmax = prob[k].gnorm; out->worst = k; }
+  }
+  if (info_out) {
+    memset(info_out, 0, sizeof(*info_out));
+    info_out->iterations = iters; info_out->evaluations = out->evals; info_out->converged = out->conv; info_out->grad_norm = out->gmax;
+    for (int k = 0; k < machines; ++k) info_out->loss[k] = prob[k].f;
+  }
+  return PLIPMI_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -150,11 +206,8 @@ int plipmi_similarity_topk(plipmi_handle h, const float* keys, int Nq, const flo
 // ---- linear-probe head (probe.hip, probe_solver.h) ----------------------------------------------------------------------
 static int probe_check(plipmi_handle h, const void* X, int N, int D, const void* WB, int K) {
   if (!h || !X || !WB) return fail(PLIPMI_ERR_INVALID, "null handle / X / WB");
-  if (N <= 0) return fail(PLIPMI_ERR_INVALID, "need N > 0 rows, got %d", N);
   if (K < 1 || K > PLIPMI_PROBE_MAX_K) return fail(PLIPMI_ERR_INVALID, "need 1 <= K <= %d problems, got %d", PLIPMI_PROBE_MAX_K, K);
-  if (D < 4 || D > 1024 || D % 4) return fail(PLIPMI_ERR_INVALID, "embedding width %d unsupported (D %% 4 == 0, 4 <= D <= 1024)", D);
-  if (reinterpret_cast<uintptr_t>(X) % 16) return fail(PLIPMI_ERR_INVALID, "X must be 16-byte aligned");
-  return PLIPMI_OK;
+  return check_embeddings("", X, N, D);
 }
 static int probe_check_fit(const void* y, const void* pos_w, const void* neg_w, float alpha) {
   if (!y || !pos_w || !neg_w) return fail(PLIPMI_ERR_INVALID, "null y / pos_w / neg_w");
@@ -193,51 +246,15 @@ int plipmi_probe_fit(plipmi_handle h, const float* X, int N, int D, const int32_
   if (max_iter < 1 || !std::isfinite(gtol) || gtol <= 0.f) return fail(PLIPMI_ERR_INVALID, "need max_iter >= 1 and a finite gtol > 0");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   RUN(probe_scratch(h, N, D, K, s));
-  const int n = D + 1;
-  const size_t wb_bytes = (size_t)K * n * 4;
-  RUN(h->probe_host.reserve(2 * align_up(wb_bytes, 256) + align_up((size_t)K * 8, 256), s));
-  float* wb_h = reinterpret_cast<float*>(h->probe_host.data());
-  float* g_h = reinterpret_cast<float*>(h->probe_host.data() + align_up(wb_bytes, 256));
-  double* l_h = reinterpret_cast<double*>(h->probe_host.data() + 2 * align_up(wb_bytes, 256));
-
-  HIP_TRY(hipMemcpyAsync(wb_h, WB_inout, wb_bytes, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  for (size_t i = 0; i < (size_t)K * n; ++i)
-    if (!std::isfinite(wb_h[i])) return fail(PLIPMI_ERR_INVALID, "the starting point WB_inout holds a non-finite value");
-  std::vector<ProbeLbfgs> prob(K);
-  for (int k = 0; k < K; ++k) prob[k].init(wb_h + (size_t)k * n, n, max_iter, (double)gtol);
-  int evals = 0;
-  // every pass evaluates the K current trial points; the trial point travels through WB_inout itself
-  for (;;) {
-    for (int k = 0; k < K; ++k) prob[k].trial(wb_h + (size_t)k * n);
-    HIP_TRY(hipMemcpyAsync(WB_inout, wb_h, wb_bytes, hipMemcpyHostToDevice, s));
-    bool all_done = true;
-    for (int k = 0; k < K; ++k) all_done = all_done && prob[k].done;
-    if (all_done) break;           // WB_inout now holds every problem's final point
-    float* grad; double* loss;
-    RUN(probe_eval(h, X, N, D, y, K, pos_w, neg_w, alpha, WB_inout, &grad, &loss, s));
-    HIP_TRY(hipMemcpyAsync(g_h, grad, wb_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(l_h, loss, (size_t)K * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    ++evals;
-    for (int k = 0; k < K; ++k) prob[k].feed(l_h[k], g_h + (size_t)k * n);
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  int iters = 0, conv = 0, worst = -1;
-  double gmax = 0;
-  for (int k = 0; k < K; ++k) {
-    iters = std::max(iters, prob[k].iters);
-    conv += prob[k].converged ? 1 : 0;
-    if (prob[k].gnorm >= gmax) { gmax = prob[k].gnorm; worst = k; }
-  }
-  if (info_out) {
-    memset(info_out, 0, sizeof(*info_out));
-    info_out->iterations = iters; info_out->evaluations = evals; info_out->converged = conv; info_out->grad_norm = gmax;
-    for (int k = 0; k < K; ++k) info_out->loss[k] = prob[k].f;
-  }
-  if (conv != K)
+  // K machines of D + 1 variables: the one-vs-rest problems are independent
+  ProbeSolve r;
+  RUN(probe_solve(h, K, D + 1, max_iter, gtol, WB_inout, info_out, s, [&](float** grad, double** loss) {
+    return probe_eval(h, X, N, D, y, K, pos_w, neg_w, alpha, WB_inout, grad, loss, s);
+  }, &r));
+  if (r.conv != K)
     return fail(PLIPMI_ERR_NOT_CONVERGED, "probe fit: %d of %d problems did not reach |grad|_inf <= %g within %d iterations "
-                "(largest %g, problem %d, %d evaluations); WB holds the best point found", K - conv, K, (double)gtol, max_iter, gmax, worst, evals);
+                "(largest %g, problem %d, %d evaluations); WB holds the best point found", K - r.conv, K, (double)gtol, max_iter, r.gmax,
+                r.worst, r.evals);
   return PLIPMI_OK;
 }
 
@@ -254,10 +271,8 @@ int plipmi_probe_predict(plipmi_handle h, const float* X, int N, int D, const fl
 // ---- softmax linear probe (probe_softmax.hip, probe_solver.h) ------------------------------------------------------------------
 static int softmax_check(plipmi_handle h, const void* X, int N, int D, const void* y, int C, float alpha, const void* WB) {
   if (!h || !X || !y || !WB) return fail(PLIPMI_ERR_INVALID, "null handle / X / y / WB");
-  if (N <= 0) return fail(PLIPMI_ERR_INVALID, "need N > 0 rows, got %d", N);
   if (C < 2 || C > PLIPMI_PROBE_MAX_K) return fail(PLIPMI_ERR_INVALID, "need 2 <= C <= %d classes, got %d", PLIPMI_PROBE_MAX_K, C);
-  if (D < 4 || D > 1024 || D % 4) return fail(PLIPMI_ERR_INVALID, "embedding width %d unsupported (D %% 4 == 0, 4 <= D <= 1024)", D);
-  if (reinterpret_cast<uintptr_t>(X) % 16) return fail(PLIPMI_ERR_INVALID, "X must be 16-byte aligned");
+  RUN(check_embeddings("", X, N, D));
   if (!std::isfinite(alpha) || alpha <= 0.f) return fail(PLIPMI_ERR_INVALID, "alpha must be finite and > 0, got %g", (double)alpha);
   return PLIPMI_OK;
 }
@@ -289,42 +304,14 @@ int plipmi_softmax_fit(plipmi_handle h, const float* X, int N, int D, const int3
   if (max_iter < 1 || !std::isfinite(gtol) || gtol <= 0.f) return fail(PLIPMI_ERR_INVALID, "need max_iter >= 1 and a finite gtol > 0");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   RUN(h->probe_ws.reserve(softmax_scratch_bytes(N, D, C), s));
-  const int n = C * (D + 1);                 // ONE problem over all the variables: the classes are coupled
-  const size_t wb_bytes = (size_t)n * 4;
-  RUN(h->probe_host.reserve(2 * align_up(wb_bytes, 256) + 256, s));
-  float* wb_h = reinterpret_cast<float*>(h->probe_host.data());
-  float* g_h = reinterpret_cast<float*>(h->probe_host.data() + align_up(wb_bytes, 256));
-  double* l_h = reinterpret_cast<double*>(h->probe_host.data() + 2 * align_up(wb_bytes, 256));
-
-  HIP_TRY(hipMemcpyAsync(wb_h, WB_inout, wb_bytes, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(wb_h[i])) return fail(PLIPMI_ERR_INVALID, "the starting point WB_inout holds a non-finite value");
-  ProbeLbfgs prob;
-  prob.init(wb_h, n, max_iter, (double)gtol);
-  int evals = 0;
-  // one evaluation per trial point; the trial point travels through WB_inout itself
-  for (;;) {
-    prob.trial(wb_h);
-    HIP_TRY(hipMemcpyAsync(WB_inout, wb_h, wb_bytes, hipMemcpyHostToDevice, s));
-    if (prob.done) break;            // WB_inout now holds the final point
-    float* grad; double* loss;
-    RUN(softmax_eval(h, X, N, D, y, C, class_w, alpha, WB_inout, &grad, &loss, s));
-    HIP_TRY(hipMemcpyAsync(g_h, grad, wb_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(l_h, loss, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    ++evals;
-    prob.feed(*l_h, g_h);
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  if (info_out) {
-    memset(info_out, 0, sizeof(*info_out));
-    info_out->iterations = prob.iters; info_out->evaluations = evals; info_out->converged = prob.converged ? 1 : 0;
-    info_out->grad_norm = prob.gnorm; info_out->loss[0] = prob.f;
-  }
-  if (!prob.converged)
+  // ONE machine over all C (D + 1) variables: the classes are coupled
+  ProbeSolve r;
+  RUN(probe_solve(h, 1, C * (D + 1), max_iter, gtol, WB_inout, info_out, s, [&](float** grad, double** loss) {
+    return softmax_eval(h, X, N, D, y, C, class_w, alpha, WB_inout, grad, loss, s);
+  }, &r));
+  if (!r.conv)
     return fail(PLIPMI_ERR_NOT_CONVERGED, "softmax fit: did not reach |grad|_inf <= %g within %d iterations (now %g, %d evaluations); "
-                "WB holds the best point found", (double)gtol, max_iter, prob.gnorm, evals);
+                "WB holds the best point found", (double)gtol, max_iter, r.gmax, r.evals);
   return PLIPMI_OK;
 }
 

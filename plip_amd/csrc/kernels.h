@@ -183,6 +183,7 @@ hipError_t launch_token_scores(const float* E, int M, int P, const float* T, int
 // then intercept) over X [N, D] fp32 with int32 labels y: problem k's positive label is class_base + k, its sample weights pos_w[k] /
 // neg_w[k].  `scratch` (probe_scratch_bytes) holds the per-workgroup partials and the results: *grad = fp32 [K, D + 1], *loss =
 // double [K] point into it.  D % 4 == 0, D <= 1024, K <= 64, X 16-byte aligned.  Deterministic: fixed-order reductions.
+// The embedding tile and what this unit, probe_softmax.hip and kmeans.hip share around it are in probe_tile.h and probe_fit_*.inc.
 size_t probe_scratch_bytes(int N, int D, int K, size_t* grad_off, size_t* loss_off, size_t* partl_off);
 hipError_t launch_probe_loss_grad(const float* X, int N, int D, const int32_t* y, const float* WB, int K, const float* pos_w,
                                   const float* neg_w, int class_base, float alpha, char* scratch, float** grad, double** loss,

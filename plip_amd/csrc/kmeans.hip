@@ -1,5 +1,7 @@
 // kmeans.hip -- k-means (Lloyd) on cached embeddings X [N, D] fp32: the entries of include/plipmi.h "k-means on cached embeddings", the
-// update-step test entry of plipmi_test.h, and their kernels.  One unit behind everything that existed: no other unit's code changes.
+// update-step test entry of plipmi_test.h, and their kernels.  One unit behind every other one (no unit of build.py's SOURCES calls into
+// it).  The tile, the centres' 16-byte operand form (ProbeTile load_centres / tile_scores), join_scores, the thread-order sum, the LDS
+// byte count and the streaming workgroup count are probe_tile.h's; the X / N / D check is handle.h's check_embeddings.
 //
 // Both metrics are ONE score with a per-centre bias: s_ik = x_i . c_k + h_k (Euclidean h_k = -1/2 |c_k|^2, cosine h_k = 0), the label
 // is the first arg-max over k, and the distance is recovered from the best score (|x_i|^2 - 2 s or 1 - s, clamped at 0).
@@ -60,16 +62,10 @@ __device__ __forceinline__ float wave_dot(const float* __restrict__ a, const flo
   return acc;
 }
 
-// the workgroup's 256 per-thread doubles summed by thread 0 in thread order and handed to every thread; `red` is LDS of 257 doubles
+// probe_tile.h's block_sum_to behind a barrier (`red` may still be read), the sum handed to every thread; `red` is LDS of 257 doubles
 __device__ __forceinline__ double block_sum_f64(double* red, double v, int tid) {
   __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0.0;
-    for (int i = 0; i < 256; ++i) s += red[i];
-    red[256] = s;
-  }
+  block_sum_to(red, v, tid, red + 256);
   __syncthreads();
   return red[256];
 }
@@ -95,48 +91,6 @@ __global__ __launch_bounds__(256) void kmeans_bias_kernel(const float* __restric
   if (lane == 0) hb[k] = (float)(-0.5 * acc);
 }
 
-// This wave's slice of the centres kbase .. kbase + 15, 16 bytes per lane and load: wave w owns columns [16 CT w, 16 CT (w + 1)), and lane
-// (n = lane & 15, q = lane >> 4) holds wf[j] = C[kbase + n][16 CT w + 16 j + 4 q .. + 3] -- a row's four lanes read 64 contiguous bytes.
-// Zeros past K and D (D % 4 == 0: a group of four is inside or outside as a whole).
-template <int CT>
-__device__ __forceinline__ void load_centres(float4 (&wf)[CT], const float* __restrict__ C, int K, int D, int kbase, int wave, int lane) {
-  const int cls = kbase + (lane & 15);
-#pragma unroll
-  for (int j = 0; j < CT; ++j) {
-    const int d = wave * 16 * CT + 16 * j + 4 * (lane >> 4);
-    wf[j] = (cls < K && d < D) ? *reinterpret_cast<const float4*>(C + (size_t)cls * D + d) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-
-// This wave's partial scores of the tile's two 16-row blocks against the slice -> zp[wave][32][16].  The MFMA's k index is free as long as
-// both operands agree on it: k-step 4 j + e of lane (m, q) is column 16 CT w + 16 j + 4 q + e, so the X side too is one 16-byte LDS read
-// per four steps (the swizzle moves whole 16-byte groups).
-template <int CT>
-__device__ __forceinline__ void tile_scores(const float* xs, const float4 (&wf)[CT], float* zp, int wave, int lane) {
-  constexpr int Dp = 64 * CT;
-  f32x4 z0 = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
-  const int m = lane & 15, q = lane >> 4, sw = probe_swz(m);      // probe_swz(m + 16) == probe_swz(m)
-#pragma unroll
-  for (int j = 0; j < CT; ++j) {
-    const int d = (wave * 16 * CT + 16 * j + 4 * q) ^ sw;
-    const float4 a0 = *reinterpret_cast<const float4*>(&xs[m * Dp + d]), a1 = *reinterpret_cast<const float4*>(&xs[(m + 16) * Dp + d]);
-    z0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, wf[j].x, z0, 0, 0, 0);
-    z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, wf[j].x, z1, 0, 0, 0);
-    z0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, wf[j].y, z0, 0, 0, 0);
-    z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, wf[j].y, z1, 0, 0, 0);
-    z0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, wf[j].z, z0, 0, 0, 0);
-    z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, wf[j].z, z1, 0, 0, 0);
-    z0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, wf[j].w, z0, 0, 0, 0);
-    z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, wf[j].w, z1, 0, 0, 0);
-  }
-  float* o = zp + wave * (kRows * kGroup);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {        // C/D layout: column (centre) = lane & 15, row = 4 (lane >> 4) + i
-    o[(4 * q + i) * kGroup + m] = z0[i];
-    o[(16 + 4 * q + i) * kGroup + m] = z1[i];
-  }
-}
-
 // labels[i] = first arg-max_k (x_i . c_k + hb[k]), scores[i] = that maximum (scores may be nullptr).  changed != nullptr: the number of
 // rows whose label differs from what `labels` held is ADDED to *changed.  grid.x workgroups walk the 32-row tiles.
 template <int CT>
@@ -160,15 +114,15 @@ __global__ __launch_bounds__(kThreads) void kmeans_assign_kernel(const float* __
   for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
     T::direct(X, N, D, t * kRows, tid, xs);
     float4 wf[CT], wn[kPrefetch ? CT : 1];
-    load_centres<CT>(wf, C, K, D, 0, wave, lane);
+    T::load_centres(wf, C, K, D, 0, wave, lane);
     __syncthreads();
     float best[2] = {-INFINITY, -INFINITY};
     int bk[2] = {0, 0};
     for (int g = 0; g < groups; ++g) {
       if constexpr (kPrefetch) {
-        if (g + 1 < groups) load_centres<CT>(wn, C, K, D, (g + 1) * kGroup, wave, lane);
+        if (g + 1 < groups) T::load_centres(wn, C, K, D, (g + 1) * kGroup, wave, lane);
       }
-      tile_scores<CT>(xs, wf, zp, wave, lane);
+      T::tile_scores(xs, wf, zp, wave, lane);
       __syncthreads();
       const int cls = g * kGroup + rc;
       if (cls < K) {
@@ -176,7 +130,7 @@ __global__ __launch_bounds__(kThreads) void kmeans_assign_kernel(const float* __
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int o = (rr + 16 * h) * kGroup + rc;
-          const float z = bias + (((zp[o] + zp[kRows * kGroup + o]) + zp[2 * kRows * kGroup + o]) + zp[3 * kRows * kGroup + o]);
+          const float z = join_scores(zp, o, bias);
           if (z > best[h]) { best[h] = z; bk[h] = cls; }      // groups ascend: an equal score keeps the lower k
         }
       }
@@ -186,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void kmeans_assign_kernel(const float* __
 #pragma unroll
           for (int j = 0; j < CT; ++j) wf[j] = wn[j];
         } else {
-          load_centres<CT>(wf, C, K, D, (g + 1) * kGroup, wave, lane);
+          T::load_centres(wf, C, K, D, (g + 1) * kGroup, wave, lane);
         }
       }
     }
@@ -556,11 +510,9 @@ int km_check(const char* who, plipmi_handle h, const void* X, int N, int D, int 
   if (!X) return fail(PLIPMI_ERR_INVALID, "%s: null X", who);
   if (metric != PLIPMI_KMEANS_EUCLIDEAN && metric != PLIPMI_KMEANS_COSINE)
     return fail(PLIPMI_ERR_INVALID, "%s: unknown metric %d (0 = euclidean, 1 = cosine)", who, metric);
-  if (N <= 0) return fail(PLIPMI_ERR_INVALID, "%s: need N > 0 rows, got %d", who, N);
-  if (D < 4 || D > 1024 || D % 4) return fail(PLIPMI_ERR_INVALID, "%s: embedding width %d unsupported (D %% 4 == 0, 4 <= D <= 1024)", who, D);
+  RUN(check_embeddings((std::string(who) + ": ").c_str(), X, N, D));
   if (K < 1 || K > PLIPMI_KMEANS_MAX_K || K > N)
     return fail(PLIPMI_ERR_INVALID, "%s: need 1 <= K <= min(N, %d) clusters, got K = %d with N = %d", who, PLIPMI_KMEANS_MAX_K, K, N);
-  if (reinterpret_cast<uintptr_t>(X) % 16) return fail(PLIPMI_ERR_INVALID, "%s: X must be 16-byte aligned", who);
   return PLIPMI_OK;
 }
 
@@ -583,18 +535,12 @@ int km_assign(plipmi_handle h, const float* X, int N, int D, const float* C, int
   hipLaunchKernelGGL(kmeans_bias_kernel, dim3((K + 3) / 4), dim3(256), 0, s, C, K, D, metric, L.hb);
   HIP_TRY(hipGetLastError());
   const long ntiles = ((long)N + kRows - 1) / kRows;
-  const int nwg = (int)std::max<long>(1, std::min<long>(ntiles, 2L * probe_workgroups(INT_MAX, D)));
+  const int nwg = probe_stream_workgroups(N, D);
   Scope sc(h, s, "kmeans_assign", 2.0 * N * (double)D * K, (double)N * D * 4 + (double)nwg * ((ntiles + nwg - 1) / nwg) * K * D * 4);
   HIP_TRY(probe_dispatch(probe_col_tiles(D), [&](auto ct) -> hipError_t {
     constexpr int CT = decltype(ct)::value;
-    const size_t lds = ((size_t)kRows * 64 * CT + 4 * kRows * kGroup) * 4;
-    static bool done = false;
-    if (!done) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&kmeans_assign_kernel<CT>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      done = true;
-    }
+    const size_t lds = probe_lds_bytes(CT, 0);
+    if (const hipError_t e = allow_lds<&kmeans_assign_kernel<CT>>(lds); e != hipSuccess) return e;
     kmeans_assign_kernel<CT><<<nwg, kThreads, lds, s>>>(X, N, D, C, K, L.hb, labels, scores, changed);
     return hipGetLastError();
   }));

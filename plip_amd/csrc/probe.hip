@@ -1,7 +1,9 @@
 // probe.hip -- the linear-probe head (reference: reproducibility/evaluation/linear_probing/linear_classifier.py, scikit-learn's
 // SGDClassifier(loss="log_loss", penalty="l2", class_weight="balanced")): one fused loss-and-gradient pass over cached
 // embeddings for all K one-vs-rest problems at once, and the predict kernel.  The solver that calls it is on the host
-// (engine.hip plipmi_probe_fit).
+// (heads.hip plipmi_probe_fit).  The tile and its helpers are probe_tile.h's; the walk of probe_loss_grad_kernel described below is text
+// shared with the softmax pass (probe_fit_setup.inc, probe_fit_walk.inc, probe_fit_rest.inc): this file keeps the kernel's per-thread
+// constants, its residual stage and its loss reduction.
 //
 //   f_k(w, b) = (1/N) sum_i c_ik log(1 + exp(-t_ik (x_i.w + b))) + alpha/2 |w|^2      t_ik = +1 if y_i == k else -1
 //
@@ -18,7 +20,8 @@
 // The LDS image of X is XOR-swizzled (column ^ probe_swz(row)) so that phase 1 (16 rows x 4 consecutive columns per wave
 // read) and phase 2 (4 rows x 16 consecutive columns) are both free of bank conflicts; a 16-byte store stays contiguous.
 // Every workgroup writes its partial G, g_b and loss to its own slot; probe_finish_kernel sums the slots in a FIXED order in
-// double (no floating-point atomics: the same inputs give the same bits), divides by N and adds the penalty's terms.
+// double (no floating-point atomics: the same inputs give the same bits), divides by N and adds the penalty's terms (the gradient
+// column is probe_tile.h's finish_grad_column, the loss tail its own).
 // More than 16 problems run as ceil(K / 16) groups on grid.y, each group a pass over X of its own.
 //
 // probe_predict_kernel<CT>: the same tile and phase 1 for every group of 16 classes; writes the decision values [N, K] (optional)
@@ -38,58 +41,18 @@ __global__ __launch_bounds__(kThreads) void probe_loss_grad_kernel(const float* 
                                                                    const float* __restrict__ WB, int K, const float* __restrict__ pos_w,
                                                                    const float* __restrict__ neg_w, int class_base,
                                                                    float* __restrict__ part_g, double* __restrict__ part_l) {
-  using T = ProbeTile<CT>;
-  constexpr int Dp = T::Dp;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* xs = lds;                                   // [32][Dp], swizzled
-  float* zp = xs + kRows * Dp;                       // [4][32][16] partial scores; at the end: the loss / g_b reduction
-  float* rs = zp + 4 * kRows * kGroup;               // [32][16] residuals
-
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int kbase = blockIdx.y * kGroup, KP = gridDim.y * kGroup;
-  const long ntiles = ((long)N + kRows - 1) / kRows;
-
-  float wf[T::KS];
-  T::load_w(wf, WB, K, D, kbase, wave, lane);
-  f32x4 g[CT];
-#pragma unroll
-  for (int j = 0; j < CT; ++j) g[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // residual stage: this thread's problem and its two rows of a tile
-  const int rc = tid & 15, rr = tid >> 4, cls = kbase + rc;
-  const bool live = cls < K;
+#include "probe_fit_setup.inc"
   const float bias = live ? WB[(size_t)cls * (D + 1) + D] : 0.f;
   const float pw = live ? pos_w[cls] : 0.f, nw = live ? neg_w[cls] : 0.f;
   const int target = class_base + cls;               // the label that is positive for this problem
   double loss = 0.0, gb = 0.0;
 
-  // D <= 512: the next tile waits in registers while this one is computed; wider rows need those registers for wf and g
-  constexpr bool kPrefetch = CT <= 8;
-  T tile;
-  long t = blockIdx.x;
-  int ynext[2] = {-1, -1};
-  auto fetch = [&](long tl) {
-    if constexpr (kPrefetch) tile.fetch(X, N, D, tl * kRows, tid);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) { const long gr = tl * kRows + rr + 16 * h; ynext[h] = gr < N ? y[gr] : -1; }
-  };
-  if (t < ntiles) fetch(t);
-  while (t < ntiles) {
-    if constexpr (kPrefetch) tile.stage(xs, tid); else T::direct(X, N, D, t * kRows, tid, xs);
-    const int ycur[2] = {ynext[0], ynext[1]};
-    __syncthreads();
-    const long next = t + gridDim.x;
-    if (next < ntiles) fetch(next);     // in flight under this tile's arithmetic
-    T::scores(xs, wf, zp, wave, lane);
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int r = rr + 16 * h;
-      const long gr = t * kRows + r;
+  auto row_fetch = [](int, long) {};                 // the label is all a row's residual needs
+  auto row_latch = [] {};
+#include "probe_fit_walk.inc"
       float res = 0.f;
       if (live && gr < N) {
-        const int o = r * kGroup + rc;
-        const float z = bias + (((zp[o] + zp[kRows * kGroup + o]) + zp[2 * kRows * kGroup + o]) + zp[3 * kRows * kGroup + o]);
+        const float z = join_scores(zp, r * kGroup + rc, bias);
         const bool pos = ycur[h] == target;
         const float c = pos ? pw : nw;
         const float e = expf(-fabsf(z));
@@ -99,44 +62,11 @@ __global__ __launch_bounds__(kThreads) void probe_loss_grad_kernel(const float* 
         res = c * (sig - (pos ? 1.f : 0.f));
         gb += (double)res;
       }
-      rs[r * kGroup + rc] = res;
-    }
-    __syncthreads();
-    // phase 2: G[problem][d] += sum_row R[row][problem] X[row][d]
-    {
-      const int m = lane & 15, k = lane >> 4;
-#pragma unroll
-      for (int q = 0; q < kRows / 4; ++q) {
-        const int row = 4 * q + k;
-        const float a = rs[row * kGroup + m];
-        const float* xr = xs + row * Dp;
-        const int sw = probe_swz(row);
-#pragma unroll
-        for (int j = 0; j < CT; ++j) g[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xr[((wave * CT + j) * 16 + m) ^ sw], g[j], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-    t = next;
-  }
-
-  // this workgroup's slot: part_g [gridDim.x][KP][D + 1], part_l [gridDim.x][KP]
-  float* pg = part_g + ((size_t)blockIdx.x * KP + kbase) * (D + 1);
-  {
-    const int m = lane & 15, k = lane >> 4;
-#pragma unroll
-    for (int j = 0; j < CT; ++j) {
-      const int d = (wave * CT + j) * 16 + m;
-      if (d < D) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pg[(size_t)(4 * k + i) * (D + 1) + d] = g[j][i];     // C/D: row (problem) = 4 (lane >> 4) + i
-      }
-    }
-  }
-  double* red = reinterpret_cast<double*>(zp);        // [2][16 row slots][16 problems] doubles = 4 KiB of zp's 8 KiB
+#include "probe_fit_rest.inc"
   red[rr * kGroup + rc] = loss;
   red[256 + rr * kGroup + rc] = gb;
   __syncthreads();
-  if (tid < kGroup) {
+  if (tid < kGroup) {                                // the problem's 16 row slots in order
     double l = 0.0, b = 0.0;
     for (int i = 0; i < 16; ++i) { l += red[i * kGroup + tid]; b += red[256 + i * kGroup + tid]; }
     pg[(size_t)tid * (D + 1) + D] = (float)b;
@@ -144,26 +74,13 @@ __global__ __launch_bounds__(kThreads) void probe_loss_grad_kernel(const float* 
   }
 }
 
-// grad[k][d] = (sum over workgroups, in order)/N + alpha W[k][d]; the intercept's has no penalty;
-// loss[k] = (sum)/N + alpha/2 |w_k|^2.  grid (K, ceil((D + 1) / 64)), 256 threads = 64 columns x 4 slices of the workgroups.
+// grad: finish_grad_column; loss[k] = (sum over workgroups)/N + alpha/2 |w_k|^2.  grid (K, ceil((D + 1) / 64)), 256 threads.
 __global__ __launch_bounds__(256) void probe_finish_kernel(const float* __restrict__ part_g, const double* __restrict__ part_l, int nwg,
                                                           int KP, const float* __restrict__ WB, int N, int D, float alpha,
                                                           float* __restrict__ grad, double* __restrict__ loss) {
   __shared__ double sh[4][64];
-  const int k = blockIdx.x, tid = threadIdx.x, c = tid & 63, q = tid >> 6;
-  const int d = blockIdx.y * 64 + c;
-  double acc = 0.0;
-  if (d <= D) {
-    const int w0 = (int)((long)nwg * q / 4), w1 = (int)((long)nwg * (q + 1) / 4);
-    for (int w = w0; w < w1; ++w) acc += (double)part_g[((size_t)w * KP + k) * (D + 1) + d];
-  }
-  sh[q][c] = acc;
-  __syncthreads();
-  if (q == 0 && d <= D) {
-    const double s = ((sh[0][c] + sh[1][c]) + sh[2][c]) + sh[3][c];
-    const double pen = d < D ? (double)alpha * (double)WB[(size_t)k * (D + 1) + d] : 0.0;
-    grad[(size_t)k * (D + 1) + d] = (float)(s / N + pen);
-  }
+  const int k = blockIdx.x, c = threadIdx.x & 63, q = threadIdx.x >> 6;
+  finish_grad_column(part_g, nwg, KP, WB, N, D, alpha, grad, sh, c, q);
   if (blockIdx.y == 0 && q == 1) {       // one wave: the loss of problem k
     double l = 0.0, w2 = 0.0;
     for (int w = c; w < nwg; w += 64) l += part_l[(size_t)w * KP + k];
@@ -203,7 +120,7 @@ __global__ __launch_bounds__(kThreads) void probe_predict_kernel(const float* __
       for (int h = 0; h < 2; ++h) {
         const int r = rr + 16 * h, o = r * kGroup + rc;
         const long gr = t * kRows + r;
-        const float z = bias + (((zp[o] + zp[kRows * kGroup + o]) + zp[2 * kRows * kGroup + o]) + zp[3 * kRows * kGroup + o]);
+        const float z = join_scores(zp, o, bias);
         if (cls < K && gr < N && decision) decision[gr * K + cls] = z;
         // column rc of the row keeps the first maximum over the problems rc, rc + 16, ... (ascending: ties keep the earlier)
         if (cls < K && (gI == 0 || z > best[o])) { best[o] = z; arg[o] = cls; }
@@ -231,9 +148,6 @@ __global__ __launch_bounds__(kThreads) void probe_predict_kernel(const float* __
     __syncthreads();
   }
 }
-
-size_t lds_fit(int CT) { return ((size_t)kRows * 64 * CT + 4 * kRows * kGroup + kRows * kGroup) * 4; }
-size_t lds_predict(int CT) { return ((size_t)kRows * 64 * CT + 4 * kRows * kGroup + 2 * kRows * kGroup) * 4; }
 
 int compute_units() {
   static int cus = 0;
@@ -283,14 +197,8 @@ hipError_t launch_probe_loss_grad(const float* X, int N, int D, const int32_t* y
   const int groups = (K + kGroup - 1) / kGroup, nwg = probe_workgroups(N, D);
   hipError_t e = probe_dispatch(probe_col_tiles(D), [&](auto ct) -> hipError_t {
     constexpr int CT = decltype(ct)::value;
-    const size_t lds = lds_fit(CT);
-    static bool attr_done = false;
-    if (!attr_done) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&probe_loss_grad_kernel<CT>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      attr_done = true;
-    }
+    const size_t lds = probe_lds_bytes(CT, kRows * kGroup);              // the residuals
+    if (const hipError_t e = allow_lds<&probe_loss_grad_kernel<CT>>(lds); e != hipSuccess) return e;
     probe_loss_grad_kernel<CT><<<dim3(nwg, groups), kThreads, lds, s>>>(X, N, D, y, WB, K, pos_w, neg_w, class_base, part_g, part_l);
     return hipGetLastError();
   });
@@ -303,14 +211,8 @@ hipError_t launch_probe_predict(const float* X, int N, int D, const float* WB, i
   const long ntiles = ((long)N + kRows - 1) / kRows;
   return probe_dispatch(probe_col_tiles(D), [&](auto ct) -> hipError_t {
     constexpr int CT = decltype(ct)::value;
-    const size_t lds = lds_predict(CT);
-    static bool attr_done = false;
-    if (!attr_done) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&probe_predict_kernel<CT>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      attr_done = true;
-    }
+    const size_t lds = probe_lds_bytes(CT, 2 * kRows * kGroup);          // best and arg
+    if (const hipError_t e = allow_lds<&probe_predict_kernel<CT>>(lds); e != hipSuccess) return e;
     const int nwg = (int)std::max<long>(1, std::min<long>(ntiles, (long)compute_units() * 4));
     probe_predict_kernel<CT><<<nwg, kThreads, lds, s>>>(X, N, D, WB, K, decision, pred);
     return hipGetLastError();

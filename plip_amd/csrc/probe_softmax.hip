@@ -7,7 +7,9 @@
 // Unlike the one-vs-rest pass of probe.hip the C problems are coupled: a row's residual needs the log-sum-exp over ALL its classes.
 //
 // The tile is probe.hip's (probe_tile.h): 32 rows of X in swizzled LDS, phase 1 Z = X_tile W^T and phase 2 G += R^T X_tile with
-// v_mfma_f32_16x16x4_f32 (exact fp32), G and the W slice in registers for the whole kernel, one partial slot per workgroup.
+// v_mfma_f32_16x16x4_f32 (exact fp32), G and the W slice in registers for the whole kernel, one partial slot per workgroup.  So is the
+// walk of softmax_loss_grad_kernel (probe_fit_setup.inc, probe_fit_walk.inc, probe_fit_rest.inc); the kernel keeps its per-thread
+// constants, the rows' statistics of the unfused form (row_fetch / row_latch), its residual stage and its loss reduction.
 //
 //   C <= 16   softmax_loss_grad_kernel<CT, true>: X is read ONCE.  The 16 classes of a row sit in 16 adjacent lanes of the residual
 //             stage (rc = tid & 15), so the row's max, its sum of exp(z - max) and its weight are four __shfl_xor steps each;
@@ -21,7 +23,8 @@
 // y is only ever COMPARED with a class index the thread owns, and cw is indexed by that index: a label outside [0, C) matches
 // nothing and gives its row weight 0.  The loss term of a row is formed in double (max + log(sum) - z_y) by the lane that owns class
 // y.  Every workgroup writes its partial G, g_b and loss to its own slot; softmax_finish_kernel sums the slots in a FIXED order in
-// double (no floating-point atomics: the same inputs give the same bits), divides by N and adds the penalty's terms.
+// double (no floating-point atomics: the same inputs give the same bits), divides by N and adds the penalty's terms (the gradient
+// column is probe_tile.h's finish_grad_column, the loss tail its own).
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -45,22 +48,6 @@ __device__ __forceinline__ float group_max(float v) {
   return v;
 }
 __device__ __forceinline__ float group_sum(float v) { return row16_sum(v); }
-
-// the four waves' partial scores of (row r, column rc) in wave order, plus the intercept
-__device__ __forceinline__ float join_scores(const float* zp, int o, float bias) {
-  return bias + (((zp[o] + zp[kRows * kGroup + o]) + zp[2 * kRows * kGroup + o]) + zp[3 * kRows * kGroup + o]);
-}
-
-// the workgroup's 256 per-thread doubles summed by thread 0 in thread order; `red` is LDS of 256 doubles
-__device__ __forceinline__ void block_sum_to(double* red, double v, int tid, double* out) {
-  red[tid] = v;
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0.0;
-    for (int i = 0; i < kThreads; ++i) s += red[i];
-    *out = s;
-  }
-}
 
 // C > 16: rowm[i] = max_k z_ik, rowsum[i] = sum_k exp(z_ik - rowm[i]), roww[i] = cw[y_i] (0: y_i outside [0, C)); part_l[workgroup] =
 // its rows' sum of roww (rowm + log rowsum - z_iy).  grid.x workgroups walk the tiles.
@@ -133,63 +120,28 @@ __global__ __launch_bounds__(kThreads) void softmax_loss_grad_kernel(const float
                                                                      const float* __restrict__ rowm, const float* __restrict__ rowsum,
                                                                      const float* __restrict__ roww, float* __restrict__ part_g,
                                                                      double* __restrict__ part_l) {
-  using T = ProbeTile<CT>;
-  constexpr int Dp = T::Dp;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* xs = lds;                                   // [32][Dp], swizzled
-  float* zp = xs + kRows * Dp;                       // [4][32][16] partial scores; at the end: the loss / g_b reduction
-  float* rs = zp + 4 * kRows * kGroup;               // [32][16] residuals
-
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int kbase = blockIdx.y * kGroup, KP = gridDim.y * kGroup;
-  const long ntiles = ((long)N + kRows - 1) / kRows;
-
-  float wf[T::KS];
-  T::load_w(wf, WB, C, D, kbase, wave, lane);
-  f32x4 g[CT];
-#pragma unroll
-  for (int j = 0; j < CT; ++j) g[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // residual stage: this thread's class and its two rows of a tile
-  const int rc = tid & 15, rr = tid >> 4, cls = kbase + rc;
-  const bool live = cls < C;
+  const int K = C;                                   // the fit walk's name for the number of problems
+#include "probe_fit_setup.inc"
   const float bias = live ? WB[(size_t)cls * (D + 1) + D] : 0.f;
   const float cwk = live ? (class_w ? class_w[cls] : 1.f) : 0.f;
   double loss = 0.0, gb = 0.0;
 
-  // D <= 512: the next tile waits in registers while this one is computed; wider rows need those registers for wf and g
-  constexpr bool kPrefetch = CT <= 8;
-  T tile;
-  long t = blockIdx.x;
-  int ynext[2] = {-1, -1};
+  // unfused: the rows' statistics travel with the labels
   float mnext[2] = {0.f, 0.f}, snext[2] = {1.f, 1.f}, wnext[2] = {0.f, 0.f};
-  auto fetch = [&](long tl) {
-    if constexpr (kPrefetch) tile.fetch(X, N, D, tl * kRows, tid);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const long gr = tl * kRows + rr + 16 * h;
-      ynext[h] = gr < N ? y[gr] : -1;
-      if constexpr (!FUSED) {
-        mnext[h] = gr < N ? rowm[gr] : 0.f;
-        snext[h] = gr < N ? rowsum[gr] : 1.f;
-        wnext[h] = gr < N ? roww[gr] : 0.f;
-      }
+  float mcur[2], scur[2], wcur[2];
+  auto row_fetch = [&](int h, long gr) {
+    if constexpr (!FUSED) {
+      mnext[h] = gr < N ? rowm[gr] : 0.f;
+      snext[h] = gr < N ? rowsum[gr] : 1.f;
+      wnext[h] = gr < N ? roww[gr] : 0.f;
     }
   };
-  if (t < ntiles) fetch(t);
-  while (t < ntiles) {
-    if constexpr (kPrefetch) tile.stage(xs, tid); else T::direct(X, N, D, t * kRows, tid, xs);
-    const int ycur[2] = {ynext[0], ynext[1]};
-    const float mcur[2] = {mnext[0], mnext[1]}, scur[2] = {snext[0], snext[1]}, wcur[2] = {wnext[0], wnext[1]};
-    __syncthreads();
-    const long next = t + gridDim.x;
-    if (next < ntiles) fetch(next);     // in flight under this tile's arithmetic
-    T::scores(xs, wf, zp, wave, lane);
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int r = rr + 16 * h;
-      const long gr = t * kRows + r;
+  auto row_latch = [&] {
+    if constexpr (!FUSED) {
+      mcur[0] = mnext[0]; mcur[1] = mnext[1]; scur[0] = snext[0]; scur[1] = snext[1]; wcur[0] = wnext[0]; wcur[1] = wnext[1];
+    }
+  };
+#include "probe_fit_walk.inc"
       const float z = join_scores(zp, r * kGroup + rc, bias);
       const bool pos = live && ycur[h] == cls;
       float m, s, w;
@@ -209,42 +161,9 @@ __global__ __launch_bounds__(kThreads) void softmax_loss_grad_kernel(const float
         const double term = ((double)m + log((double)s)) - (double)z;
         if (pos && gr < N) loss += (double)cwk * term;
       }
-      rs[r * kGroup + rc] = res;
-    }
-    __syncthreads();
-    // phase 2: G[class][d] += sum_row R[row][class] X[row][d]
-    {
-      const int m = lane & 15, k = lane >> 4;
-#pragma unroll
-      for (int q = 0; q < kRows / 4; ++q) {
-        const int row = 4 * q + k;
-        const float a = rs[row * kGroup + m];
-        const float* xr = xs + row * Dp;
-        const int sw = probe_swz(row);
-#pragma unroll
-        for (int j = 0; j < CT; ++j) g[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xr[((wave * CT + j) * 16 + m) ^ sw], g[j], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-    t = next;
-  }
-
-  // this workgroup's slot
-  float* pg = part_g + ((size_t)blockIdx.x * KP + kbase) * (D + 1);
-  {
-    const int m = lane & 15, k = lane >> 4;
-#pragma unroll
-    for (int j = 0; j < CT; ++j) {
-      const int d = (wave * CT + j) * 16 + m;
-      if (d < D) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pg[(size_t)(4 * k + i) * (D + 1) + d] = g[j][i];     // C/D: row (class) = 4 (lane >> 4) + i
-      }
-    }
-  }
-  double* red = reinterpret_cast<double*>(zp);        // [2][256] doubles = 4 KiB of zp's 8 KiB
+#include "probe_fit_rest.inc"
   red[kThreads + rr * kGroup + rc] = gb;
-  if constexpr (FUSED) block_sum_to(red, loss, tid, part_l + blockIdx.x); else __syncthreads();
+  if constexpr (FUSED) block_sum_to(red, loss, tid, part_l + blockIdx.x); else __syncthreads();      // part_l [gridDim.x], in thread order
   if (tid < kGroup) {
     double b = 0.0;
     for (int i = 0; i < 16; ++i) b += red[kThreads + i * kGroup + tid];
@@ -252,27 +171,14 @@ __global__ __launch_bounds__(kThreads) void softmax_loss_grad_kernel(const float
   }
 }
 
-// grad[k][d] = (sum over workgroups, in order) / N + alpha W[k][d]; the intercepts have no penalty.  grid (C, ceil((D + 1) / 64)),
-// 256 threads = 64 columns x 4 slices of the workgroups.  Workgroup (0, 0) then forms f = (sum of the nl loss slots) / N +
-// alpha/2 |W|_F^2 with all its threads.
+// grad: finish_grad_column.  grid (C, ceil((D + 1) / 64)), 256 threads.  Workgroup (0, 0) then forms f = (sum of the nl loss slots) / N
+// + alpha/2 |W|_F^2 with all its threads.
 __global__ __launch_bounds__(256) void softmax_finish_kernel(const float* __restrict__ part_g, const double* __restrict__ part_l, int nwg,
                                                             int nl, int KP, const float* __restrict__ WB, int N, int C, int D,
                                                             float alpha, float* __restrict__ grad, double* __restrict__ loss) {
   __shared__ double sh[4][64];
-  const int k = blockIdx.x, tid = threadIdx.x, c = tid & 63, q = tid >> 6;
-  const int d = blockIdx.y * 64 + c;
-  double acc = 0.0;
-  if (d <= D) {
-    const int w0 = (int)((long)nwg * q / 4), w1 = (int)((long)nwg * (q + 1) / 4);
-    for (int w = w0; w < w1; ++w) acc += (double)part_g[((size_t)w * KP + k) * (D + 1) + d];
-  }
-  sh[q][c] = acc;
-  __syncthreads();
-  if (q == 0 && d <= D) {
-    const double s = ((sh[0][c] + sh[1][c]) + sh[2][c]) + sh[3][c];
-    const double pen = d < D ? (double)alpha * (double)WB[(size_t)k * (D + 1) + d] : 0.0;
-    grad[(size_t)k * (D + 1) + d] = (float)(s / N + pen);
-  }
+  const int tid = threadIdx.x, c = tid & 63, q = tid >> 6;
+  finish_grad_column(part_g, nwg, KP, WB, N, D, alpha, grad, sh, c, q);
   if (blockIdx.x == 0 && blockIdx.y == 0) {
     __syncthreads();
     double l = 0.0, w2 = 0.0;
@@ -287,20 +193,14 @@ __global__ __launch_bounds__(256) void softmax_finish_kernel(const float* __rest
   }
 }
 
-size_t lds_grad(int CT) { return ((size_t)kRows * 64 * CT + 4 * kRows * kGroup + kRows * kGroup) * 4; }
-size_t lds_stats(int CT) { return ((size_t)kRows * 64 * CT + 4 * kRows * kGroup + kRows * kMaxC) * 4; }
-
-// workgroups of the statistics pass: it keeps no accumulators, two per compute unit hide its loads
-int stats_workgroups(int N, int D) {
-  const long ntiles = ((long)N + kRows - 1) / kRows;
-  return (int)std::max<long>(1, std::min<long>(ntiles, 2L * probe_workgroups(INT_MAX, D)));
-}
+constexpr size_t lds_grad(int CT) { return probe_lds_bytes(CT, kRows * kGroup); }       // the residuals
+constexpr size_t lds_stats(int CT) { return probe_lds_bytes(CT, kRows * kMaxC); }       // the tile's scores, every class
 
 struct SoftmaxScratch { size_t part_l, grad, loss, rowm, rowsum, roww, total; };
 
 SoftmaxScratch softmax_layout(int N, int D, int C) {
   const size_t KP = (size_t)((C + kGroup - 1) / kGroup) * kGroup, nwg = probe_workgroups(N, D);
-  const size_t nl = C > kGroup ? (size_t)stats_workgroups(N, D) : nwg;
+  const size_t nl = C > kGroup ? (size_t)probe_stream_workgroups(N, D) : nwg;
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
   SoftmaxScratch L;
   size_t off = up(nwg * KP * (D + 1) * 4);
@@ -313,13 +213,6 @@ SoftmaxScratch softmax_layout(int N, int D, int C) {
   L.roww = off;   off += rows;
   L.total = off;
   return L;
-}
-
-template <typename K> hipError_t allow_lds(K kernel, size_t lds, bool* done) {
-  if (*done) return hipSuccess;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e == hipSuccess) *done = true;
-  return e;
 }
 
 }  // namespace
@@ -337,20 +230,18 @@ hipError_t launch_softmax_loss_grad(const float* X, int N, int D, const int32_t*
   *grad = reinterpret_cast<float*>(scratch + L.grad);
   *loss = reinterpret_cast<double*>(scratch + L.loss);
   const int groups = (C + kGroup - 1) / kGroup, nwg = probe_workgroups(N, D);
-  const int nl = groups > 1 ? stats_workgroups(N, D) : nwg;
+  const int nl = groups > 1 ? probe_stream_workgroups(N, D) : nwg;
   const hipError_t e = probe_dispatch(probe_col_tiles(D), [&](auto ct) -> hipError_t {
     constexpr int CT = decltype(ct)::value;
     hipError_t e;
     if (groups == 1) {
-      static bool done = false;
-      if ((e = allow_lds(&softmax_loss_grad_kernel<CT, true>, lds_grad(CT), &done)) != hipSuccess) return e;
+      if ((e = allow_lds<&softmax_loss_grad_kernel<CT, true>>(lds_grad(CT))) != hipSuccess) return e;
       softmax_loss_grad_kernel<CT, true><<<dim3(nwg, 1), kThreads, lds_grad(CT), s>>>(X, N, D, y, WB, C, class_w, nullptr, nullptr, nullptr,
                                                                                       part_g, part_l);
       return hipGetLastError();
     }
-    static bool done_s = false, done_g = false;
-    if ((e = allow_lds(&softmax_stats_kernel<CT>, lds_stats(CT), &done_s)) != hipSuccess) return e;
-    if ((e = allow_lds(&softmax_loss_grad_kernel<CT, false>, lds_grad(CT), &done_g)) != hipSuccess) return e;
+    if ((e = allow_lds<&softmax_stats_kernel<CT>>(lds_stats(CT))) != hipSuccess) return e;
+    if ((e = allow_lds<&softmax_loss_grad_kernel<CT, false>>(lds_grad(CT))) != hipSuccess) return e;
     softmax_stats_kernel<CT><<<nl, kThreads, lds_stats(CT), s>>>(X, N, D, y, WB, C, class_w, rowm, rowsum, roww, part_l);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     softmax_loss_grad_kernel<CT, false><<<dim3(nwg, groups), kThreads, lds_grad(CT), s>>>(X, N, D, y, WB, C, class_w, rowm, rowsum, roww,
