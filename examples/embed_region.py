@@ -46,6 +46,14 @@ def main():
     # half-overlapping 448 px tiles, resized on the GPU to the model's 224 px exactly as encode_images resizes such crops
     big = plip.encode_region(region, tile_px=448, stride=224, min_tissue=0.75)
     print(f"448 px tiles every 224 px, >= 75 % tissue: grid {big.grid}, {len(big.kept)} kept")
+    # stain-normalised: ONE Macenko fit over a subsample of the region (every step-th pixel of every step-th row, taken on the host
+    # before the upload), then every gathered batch normalised to the reference stains on the GPU before it is encoded
+    fit = plip.fit_stain(region)
+    row = fit.numpy()[0]
+    print(f"stain fit on every {fit.step}th pixel: {int(row[14])} tissue pixels, valid {bool(row[15])}, maxC {row[12]:.3f} {row[13]:.3f}")
+    normed = plip.encode_region(region, stain=fit)
+    cos = (normed.embeddings * out.embeddings).sum(axis=1) / (np.linalg.norm(normed.embeddings, axis=1) * np.linalg.norm(out.embeddings, axis=1))
+    print(f"with stain=: the same {len(normed.kept)} tiles, cosine to the raw tiles' embeddings {cos.min():.3f} .. {cos.max():.3f}")
 
 
 if __name__ == "__main__":

@@ -567,6 +567,41 @@ int plipmi_kmeans_fit(plipmi_handle h, const float* X, int N, int D, int K, int 
                       float* centers_inout, int32_t* labels, float* scores, int32_t* counts, int32_t* reps, plipmi_kmeans_info* info,
                       void* stream);
 
+/* ---- stain normalisation -----------------------------------------------------
+ * (Additive, like the entries above it: the version number and every existing entry are unchanged; a caller probes for the symbols.)
+ * Macenko's method on uint8 RGB images, the project's own definition (plip_amd/preprocess.py stain_fit_reference /
+ * stain_apply_reference is its float64 numpy statement; csrc/stain.hip).  Sources are strided like plipmi_warp_u8's: B images of
+ * H x W pixels, rows pitch_bytes >= 3 W apart, images image_stride_bytes apart, rows and images starting at any byte, one image below
+ * 2 GiB.  lut_dev: double [256] on the device, lut[v] = -log((v + 1) / Io), built by the CALLER (numpy) so that a pixel's optical
+ * density is the oracle's bit for bit; the device takes no logarithm.  All arithmetic is fp64 without contraction; every
+ * floating-point sum has a fixed order, the only atomics are integer: the same input gives the same bits on every run.
+ *
+ * plipmi_stain_fit: fits over the SAMPLED pixels (y % step == 0 and x % step == 0) of each image, or with pooled != 0 ONE fit over
+ * those of all B images (image, row, column order).  A pixel is tissue when no channel's density is below beta; mean and sample
+ * covariance of the n tissue densities; its two principal eigenvectors by cyclic Jacobi, each negated when its components sum below
+ * zero; the angle atan2 of every tissue pixel in that plane as a float32 key; the alpha-th and (100 - alpha)-th percentile of the keys
+ * (numpy's default linear method, the order statistics selected EXACTLY by a radix select, interpolated in fp64); the two stain
+ * vectors, haematoxylin (the larger first component) first, HE [3,2]; P = (HE^T HE)^-1 HE^T [2,3]; maxC[j] = the 99th percentile of the
+ * float32 keys (P . OD)[j] over EVERY sampled pixel.  fits_out: double [F, 16] on the device, F = pooled ? 1 : B, a row = HE (6,
+ * row-major), P (6, row-major), maxC (2), n, valid.  A fit is INVALID (valid = 0, n kept, the rest zero) when n < 16, det(HE^T HE) is
+ * not > 1e-12 or a maxC is not > 0: flagged, never a fault or a NaN.  workspace: plipmi_stain_workspace(B, H, W, step) bytes of the
+ * caller's, 16-byte aligned; it holds nothing between calls.
+ * plipmi_stain_apply: every pixel (not only the sampled ones) of image b by fit row b (n_fits == B) or row 0 (n_fits == 1):
+ * C = P . lut[rgb], C2[j] = C[j] * (target maxC[j] / maxC[j]), out[c] = min(255, Io exp(-(HE_t[c][0] C2[0] + HE_t[c][1] C2[1])))
+ * truncated to a byte; target_dev: double [8] on the device = the target's HE (6, row-major) and maxC (2).  An image whose fit is
+ * invalid is copied unchanged.  dst: uint8 [B, H, W, 3] contiguous; dwords are stored where W % 4 == 0 and dst is 4-byte aligned, and
+ * loaded where src, pitch_bytes and image_stride_bytes are multiples of 4 as well; bytes otherwise.
+ * Both only enqueue: no synchronisation, no allocation; B == 0 launches nothing.  PLIPMI_ERR_INVALID with a message, before any
+ * launch: a null pointer, H or W < 1, step < 1, pitch_bytes < 3 W, an image of 2 GiB or more, more than 2^31 - 8193 sampled pixels
+ * in a call, n_fits neither 1 nor B, alpha outside (0, 50), Io or beta not positive, a double buffer that is not 8-byte aligned. */
+size_t plipmi_stain_workspace(int B, int H, int W, int step);   /* 0 for sizes the fit refuses */
+int plipmi_stain_fit(plipmi_handle h, const uint8_t* src, int B, int H, int W, int64_t pitch_bytes, int64_t image_stride_bytes, int step,
+                     int pooled, double Io, double alpha, double beta, const double* lut_dev, void* workspace, double* fits_out,
+                     void* stream);
+int plipmi_stain_apply(plipmi_handle h, const uint8_t* src, int B, int H, int W, int64_t pitch_bytes, int64_t image_stride_bytes,
+                       const double* fits, int n_fits, const double* target_dev, double Io, const double* lut_dev, uint8_t* dst,
+                       void* stream);
+
 /* ---- measurement ------------------------------------------------------------
  * (kernel-level test entries and A/B hooks live in plipmi_test.h: same library, not part of the product interface) */
 /* Per-kernel timing with HIP events recorded on the launch stream.  While

@@ -243,6 +243,15 @@ int plipmi_softmax_loss_grad(plipmi_handle h, const float* X, int N, int D, cons
 int plipmi_kmeans_update(plipmi_handle h, const float* X, int N, int D, const int32_t* labels, const float* scores, int K, int metric,
                          float* sums, int32_t* counts, int32_t* reps, double* inertia, void* stream);
 
+/* The exact percentile of the stain fit alone (csrc/stain.hip), for tests/test_gpu_stain.py: keys fp32 [S, n] on the device, S segments
+ * of n keys, a NaN = an absent key -> out double [S, Q] = numpy's default (linear) percentile q_host[i] (HOST doubles in [0, 100],
+ * 1 <= Q <= 8) of the present keys of each segment (NaN for a segment without any), counts int32 [S] (may be NULL) = the present keys.
+ * The order statistics are selected exactly (radix select on the order-preserving integer image of a key); the interpolation is fp64.
+ * workspace: as many bytes as plipmi.h's plipmi_stain_workspace gives for (S, 1, n, 1), 16-byte aligned.  Device buffers; deterministic; enqueues only; S == 0
+ * launches nothing; anything else outside these limits is PLIPMI_ERR_INVALID before any launch. */
+int plipmi_stain_percentile(plipmi_handle h, const float* keys, int S, int n, const double* q_host, int Q, double* out, int32_t* counts,
+                            void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

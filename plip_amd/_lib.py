@@ -129,6 +129,7 @@ TEST_SYMBOLS = {
     "plipmi_token_scores": (_i, [_vp, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
     "plipmi_softmax_loss_grad": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp]),
     "plipmi_kmeans_update": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "plipmi_stain_percentile": (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_double), _i, _vp, _vp, _vp, _vp]),
 }
 # every symbol include/plipmi.h declares (the product interface): (restype, argtypes)
 SYMBOLS = {
@@ -168,6 +169,9 @@ SYMBOLS = {
     "plipmi_kmeans_seed": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_double), _vp, _vp, _vp]),
     "plipmi_kmeans_assign": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "plipmi_kmeans_fit": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, C.POINTER(KMeansInfo), _vp]),
+    "plipmi_stain_workspace": (C.c_size_t, [_i, _i, _i, _i]),
+    "plipmi_stain_fit": (_i, [_vp, _vp, _i, _i, _i, C.c_int64, C.c_int64, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
+    "plipmi_stain_apply": (_i, [_vp, _vp, _i, _i, _i, C.c_int64, C.c_int64, _vp, _i, _vp, C.c_double, _vp, _vp, _vp]),
     "plipmi_profile_enable": (_i, [_vp, _i]),
     "plipmi_profile_read": (_i, [_vp, C.POINTER(KernelStat), _i, C.POINTER(_i)]),
 }

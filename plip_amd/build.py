@@ -36,6 +36,9 @@ SOURCES = ["engine.hip", "towers.hip", "heads.hip", "test_entries.hip", "gemm.hi
 # must therefore be one that no unit of SOURCES calls into).
 # k-means on cached embeddings (assignment, update, finalise, seeding) and its entries: behind everything that existed, like the units above
 LATER_SOURCES = ["kmeans.hip"]
+# LATER_SOURCES is closed too (tests/test_kmeans_host.py pins its tail); what comes after it goes here, under the same rule.
+# Macenko stain normalisation (moments, basis, keys, the exact percentile's radix select, apply) and its entries
+STAIN_SOURCES = ["stain.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-Wno-unused-value"]
 
@@ -88,7 +91,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     hdr_digest = _digest(headers)
     jobs = []
     objs = []
-    for src in SOURCES + LATER_SOURCES:
+    for src in SOURCES + LATER_SOURCES + STAIN_SOURCES:
         obj = os.path.join(BUILD, src.replace(".hip", ".o"))
         stamp = obj + ".sha"
         want = _digest([os.path.join(CSRC, src)]) + hdr_digest

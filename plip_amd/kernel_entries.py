@@ -301,6 +301,44 @@ def kmeans_update(engine, x: torch.Tensor, labels: torch.Tensor, scores: torch.T
                                             _ptr(reps), _ptr(inertia), _stream_ptr(x.device)), "plipmi_kmeans_update")
 
 
+def stain_percentile(engine, keys: torch.Tensor, q, out: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None):
+    """The exact percentile of the stain fit alone (include/plipmi_test.h ``plipmi_stain_percentile``): keys fp32 [S, n] on the
+    engine's device (NaN = absent), ``q`` percentiles in [0, 100] -> (out double [S, Q], counts int32 [S]), written INTO the caller's
+    buffers where given (a test hangs sentinels around them)."""
+    import ctypes as C_
+    lib = _lib.load()
+    assert keys.is_cuda and keys.dtype == torch.float32 and keys.is_contiguous() and keys.dim() == 2
+    S, n = keys.shape
+    qs = (C_.c_double * len(q))(*[float(v) for v in q])
+    if out is None:
+        out = torch.empty((S, len(q)), dtype=torch.float64, device=keys.device)
+    if counts is None:
+        counts = torch.empty((S,), dtype=torch.int32, device=keys.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= S * len(q)
+    assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= S
+    with torch.cuda.device(keys.device):
+        ws = torch.empty((max(int(lib.plipmi_stain_workspace(max(S, 1), 1, max(n, 1), 1)), 16),), dtype=torch.uint8, device=keys.device)
+        _lib.check(lib.plipmi_stain_percentile(engine._h, _ptr(keys), S, n, qs, len(q), _ptr(out), _ptr(counts), _ptr(ws),
+                                               _stream_ptr(keys.device)), "plipmi_stain_percentile")
+    return out, counts
+
+
+def stain_apply_into(engine, src: torch.Tensor, fits: torch.Tensor, target: torch.Tensor, lut: torch.Tensor, dst: torch.Tensor, Io: float = 240.0,
+                     pitch: Optional[int] = None, image_stride: Optional[int] = None) -> torch.Tensor:
+    """``plipmi_stain_apply`` INTO the caller's ``dst`` (uint8, at least B * H * W * 3 bytes from its first element, guard bytes around
+    it if the test wants them): src uint8 [B,H,W,3] view with last strides (3, 1), fits double [1 or B, 16], target double [8], lut
+    double [256], all on the engine's device.  ``pitch`` / ``image_stride`` override what the view's strides say (to be refused)."""
+    lib = _lib.load()
+    assert src.is_cuda and src.dtype == torch.uint8 and src.dim() == 4 and dst.is_cuda and dst.dtype == torch.uint8
+    B, H, W = (int(v) for v in src.shape[:3])
+    p = (int(src.stride(1)) if H > 1 else 3 * W) if pitch is None else int(pitch)
+    st = (int(src.stride(0)) if B > 1 else H * p) if image_stride is None else int(image_stride)
+    with torch.cuda.device(src.device):
+        _lib.check(lib.plipmi_stain_apply(engine._h, _ptr(src), B, H, W, p, st, _ptr(fits), int(fits.shape[0]), _ptr(target), float(Io), _ptr(lut),
+                                          _ptr(dst), _stream_ptr(src.device)), "plipmi_stain_apply")
+    return dst
+
+
 # ---- the kernels around the GEMMs (include/plipmi_test.h, tests/test_gpu_small_kernels.py) ---------------------------------------------
 def _f32(*ts):
     for t in ts:

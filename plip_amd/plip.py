@@ -179,7 +179,7 @@ class PLIP:
 
     def encode_region(self, region, tile_px: Optional[int] = None, stride: Optional[int] = None, origin=(0, 0),
                       min_tissue: float = 0.5, sat_min: int = 18, luma_min: int = 25, luma_max: int = 235,
-                      image_size: Optional[int] = None, band_rows: Optional[int] = None):
+                      image_size: Optional[int] = None, band_rows: Optional[int] = None, stain=None):
         """(extension) A slide region -> the embeddings of its tissue tiles; the grid, the background filter and the stacking run on the
         GPU (region_routes.py).  ``region``: uint8 [H,W,3] -- a device tensor (any row stride: a view of a larger array is read where it
         is), or a numpy array / ``np.memmap`` / PIL image on the host, uploaded in bands of ``band_rows`` whole tile-rows (default: what a
@@ -190,12 +190,68 @@ class PLIP:
         resolution are resized on the GPU exactly as ``encode_images`` resizes a host list of such crops; ``image_size`` selects the
         resolution as it does there.  Returns a ``RegionEmbeddings``: ``embeddings`` float32 [K,P] (un-normalised, bit for bit what
         ``encode_images`` gives for the same crops), ``coords`` int64 [K,2], ``kept`` int64 [K], ``grid`` (rows, cols), ``tissue``
-        float32 [rows, cols].  An empty grid or a region without tissue gives K = 0."""
+        float32 [rows, cols].  An empty grid or a region without tissue gives K = 0.  ``stain``: a one-row ``StainFit``
+        (``fit_stain(region)``) -- every gathered batch is stain-normalised with it (``stain.stain_apply``, default target) between the
+        gather and the resize, in the lane that encodes it; the embeddings are bit for bit ``encode_images`` of the normalised crops.
+        Tissue selection still sees the raw pixels.  None: exactly the path without the keyword."""
         from .region_routes import encode_region
         n_px = self.model.config.image_size if image_size is None else int(image_size)
         eng = self.model.engine if image_size is None else self.model.engine.at_resolution(n_px, n_px)
         return encode_region(eng, region, n_px, self.model.config.projection_dim, _CROP, tile_px=tile_px, stride=stride, origin=origin,
-                             min_tissue=min_tissue, sat_min=sat_min, luma_min=luma_min, luma_max=luma_max, band_rows=band_rows)
+                             min_tissue=min_tissue, sat_min=sat_min, luma_min=luma_min, luma_max=luma_max, band_rows=band_rows, stain=stain)
+
+    def fit_stain(self, images_or_region, pooled: bool = True, step: Optional[int] = None, **params):
+        """(extension) Macenko stain fit on the GPU (stain.py ``stain_fit``; ``params``: ``Io``, ``alpha``, ``beta``).
+        ``images_or_region``: uint8 [H,W,3] (a region or one tile) or [B,H,W,3] (tiles of one size) -- a device tensor (read where it
+        lies, any row stride), a host tensor / numpy array / ``np.memmap``, or a list of equal-size arrays.  ``pooled`` (default): ONE fit
+        over all of it -- what ``encode_region(stain=...)`` and a whole slide's tiles want; False: one per image.  The fit looks at
+        the pixels with ``y % step == 0 and x % step == 0``; ``step`` None is the smallest that keeps them at or under 2^22.  A host
+        array is subsampled on the host (``[::step, ::step]``) BEFORE the upload and fitted with step 1: the same pixels in the same
+        order, so the same bits as the device-subsampled fit, for 1 / step^2 of the upload.  Returns a ``stain.StainFit`` (rows on the
+        device; nothing synchronises)."""
+        from .preprocess import stain_default_step
+        from .stain import _check_params, stain_fit
+        x = images_or_region
+        if isinstance(x, (list, tuple)):
+            x = np.stack([np.asarray(i, dtype=np.uint8) for i in x]) if len(x) else np.zeros((0, 1, 1, 3), np.uint8)
+        on_device = torch.is_tensor(x) and x.is_cuda
+        if not on_device and not torch.is_tensor(x):
+            x = np.asarray(x)                     # (a memmap stays one: only the sampled pixels are read below)
+        shape = tuple(x.shape)
+        if x.dtype != (torch.uint8 if torch.is_tensor(x) else np.uint8) or len(shape) not in (3, 4) or shape[-1] != 3:
+            raise ValueError(f"stain images are uint8 [B,H,W,3] or [H,W,3], got {x.dtype} {shape}")
+        B, H, W = (1,) + shape[:2] if len(shape) == 3 else shape[:3]
+        if step is None:
+            step = stain_default_step(max(B, 1), max(H, 1), max(W, 1))
+        _check_params(step, params.get("Io", 240.0), params.get("alpha", 1.0), params.get("beta", 0.15))
+        step = int(step)
+        eng = self.model.engine
+        if on_device:
+            return stain_fit(eng, x, pooled=pooled, step=step, **params)
+        sub = x[::step, ::step] if len(shape) == 3 else x[:, ::step, ::step]
+        sub = np.ascontiguousarray(sub.numpy() if torch.is_tensor(sub) else sub)
+        fit = stain_fit(eng, sub, pooled=pooled, step=1, **params)
+        fit.step = step
+        return fit
+
+    def normalize_stain(self, images, fit="tile", target=None) -> torch.Tensor:
+        """(extension) Stain-normalised tiles, uint8 [B,H,W,3] on the device -- what ``encode_images`` takes.  ``images``: uint8
+        [B,H,W,3] tiles of one size (array, tensor on either side, or a list).  ``fit``: "tile" (each tile by its own fit), "pooled"
+        (one fit over all of them) or a ``StainFit`` of 1 or B rows (``fit_stain``).  ``target``: None = Macenko's reference, or a
+        one-row ``StainFit`` to normalise to another slide.  A tile whose fit is invalid (hardly any tissue) comes back unchanged."""
+        from .stain import StainFit, _check_images, stain_apply, stain_fit
+        if not isinstance(fit, StainFit) and fit not in ("tile", "pooled"):
+            raise ValueError(f"fit must be 'tile', 'pooled' or a StainFit, got {fit!r}")
+        if isinstance(images, (list, tuple)):
+            images = np.stack([np.asarray(i, dtype=np.uint8) for i in images]) if len(images) else np.zeros((0, 1, 1, 3), np.uint8)
+        x, single = _check_images(images)
+        if single:
+            raise ValueError("normalize_stain takes a batch [B,H,W,3]")
+        eng = self.model.engine
+        x = x if x.device == eng.device else x.contiguous().to(eng.device)
+        if not isinstance(fit, StainFit):
+            fit = stain_fit(eng, x, pooled=fit == "pooled", step=1)
+        return stain_apply(eng, x, fit, target=target)
 
     def cluster_embeddings(self, embeddings, n_clusters: int, metric: str = "cosine", **kw):
         """(extension) K-means on cached embeddings [N,P] (numpy or torch, host or device) on the GPU (kmeans.py ``kmeans_fit``, whose

@@ -458,6 +458,194 @@ def train_view_reference(src: np.ndarray, window, affine, perspective, fill=127)
     return warp_reference(warp_reference(src, affine, False, (n, n), fill, window), perspective, True, (n, n), fill)
 
 
+# ---- Macenko stain normalisation: the definition csrc/stain.hip implements, in float64 numpy -----------------
+STAIN_IO, STAIN_ALPHA, STAIN_BETA = 240.0, 1.0, 0.15
+HE_REF = np.array([[0.5626, 0.2159], [0.7201, 0.8012], [0.4062, 0.5581]], np.float64)     # Macenko's target stain vectors (H, E columns)
+MAXC_REF = np.array([1.9705, 1.0308], np.float64)                                           # and 99th-percentile concentrations
+STAIN_MIN_TISSUE = 16          # a fit over fewer tissue pixels is invalid
+STAIN_MIN_DET = 1e-12          # and so is one whose det(HE^T HE) is not above this
+STAIN_MAX_SAMPLES = 1 << 22    # PLIP.fit_stain's default step keeps the sampled pixels at or under this
+
+
+def stain_lut(Io: float = STAIN_IO) -> np.ndarray:
+    """float64 [256]: the optical density of a byte, ``-log((v + 1) / Io)``.  Built here and uploaded: the device takes no logarithm."""
+    return -np.log((np.arange(256, dtype=np.float64) + 1.0) / np.float64(Io))
+
+
+def stain_percentile(keys, q: float) -> float:
+    """numpy's default (linear) percentile of float32 keys, written out: sort as float32, then in float64 ``r = (q / 100) (m - 1)``,
+    ``l = floor(r)``, ``t = r - l`` and numpy's two-sided lerp between ``a[l]`` and ``a[min(l + 1, m - 1)]`` (``a + (b - a) t`` below
+    ``t = 0.5``, ``b - (b - a)(1 - t)`` from there on), every operation rounded once.  NaN for no keys."""
+    a = np.sort(np.asarray(keys, dtype=np.float32).reshape(-1)).astype(np.float64)
+    m = a.size
+    if m == 0:
+        return float("nan")
+    r = (np.float64(q) / np.float64(100.0)) * np.float64(m - 1)
+    lo = int(np.floor(r))
+    t = r - np.float64(lo)
+    va, vb = a[min(lo, m - 1)], a[min(lo + 1, m - 1)]
+    d = vb - va
+    return float(va + d * t) if t < 0.5 else float(vb - d * (np.float64(1.0) - t))
+
+
+def _stain_jacobi(cov: np.ndarray):
+    """Cyclic Jacobi on a symmetric 3 x 3 (the rotation of Numerical Recipes' jacobi, at most 16 sweeps, pairs (0,1), (0,2), (1,2)) ->
+    (eigenvalues [3], eigenvectors as columns [3,3]); the statement order is the kernel's."""
+    A = np.array(cov, np.float64)
+    V = np.eye(3)
+    for _ in range(16):
+        if A[0, 1] * A[0, 1] + A[0, 2] * A[0, 2] + A[1, 2] * A[1, 2] == 0.0:
+            break
+        for p, q in ((0, 1), (0, 2), (1, 2)):
+            apq = A[p, q]
+            if apq == 0.0:
+                continue
+            theta = (A[q, q] - A[p, p]) / (2.0 * apq)
+            with np.errstate(over="ignore"):                 # (theta^2 may pass the range: then t = 0, as on the device)
+                t = 1.0 / (abs(theta) + np.sqrt(theta * theta + 1.0))
+            if theta < 0.0:
+                t = -t
+            c = 1.0 / np.sqrt(t * t + 1.0)
+            s = t * c
+            r = 3 - p - q
+            A[p, p] = A[p, p] - t * apq
+            A[q, q] = A[q, q] + t * apq
+            A[p, q] = A[q, p] = 0.0
+            arp, arq = A[r, p], A[r, q]
+            A[r, p] = A[p, r] = c * arp - s * arq
+            A[r, q] = A[q, r] = s * arp + c * arq
+            for k in range(3):
+                vkp, vkq = V[k, p], V[k, q]
+                V[k, p] = c * vkp - s * vkq
+                V[k, q] = s * vkp + c * vkq
+    return np.array([A[0, 0], A[1, 1], A[2, 2]]), V
+
+
+def _stain_samples(images: np.ndarray, step: int) -> np.ndarray:
+    """uint8 [B,H,W,3] -> the sampled pixels (y % step == 0 and x % step == 0) of every image, in image, row, column order: [B, ns, 3]"""
+    x = np.asarray(images)
+    if x.dtype != np.uint8 or x.ndim != 4 or x.shape[3] != 3:
+        raise ValueError(f"stain images are uint8 [B,H,W,3], got {x.dtype} {tuple(x.shape)}")
+    if int(step) < 1:
+        raise ValueError(f"step must be at least 1, got {step}")
+    x = x[:, ::int(step), ::int(step)]
+    return x.reshape(x.shape[0], -1, 3)
+
+
+def _stain_fit_pixels(px: np.ndarray, Io: float, alpha: float, beta: float) -> np.ndarray:
+    """One fit over pixels uint8 [m, 3] -> the float64 [16] row of ``plipmi_stain_fit``: HE [3,2], P [2,3], maxC [2], n, valid."""
+    row = np.zeros(16, np.float64)
+    od = stain_lut(Io)[px]                                            # [m, 3]
+    tissue = ~(od < beta).any(axis=1)
+    n = int(tissue.sum())
+    row[14] = n
+    if n < STAIN_MIN_TISSUE:
+        return row
+    odt = od[tissue]
+    s1 = odt.sum(axis=0)
+    cov = np.empty((3, 3))
+    for i in range(3):
+        for j in range(3):
+            cov[i, j] = ((odt[:, i] * odt[:, j]).sum() - s1[i] * s1[j] / n) / (n - 1)
+    w, V = _stain_jacobi(cov)
+    i1 = int(np.argmax(w))                                            # (ties: the lower index, as the kernel)
+    rest = [i for i in range(3) if i != i1]
+    i2 = rest[0] if w[rest[0]] >= w[rest[1]] else rest[1]
+    e = np.stack([V[:, i1], V[:, i2]], axis=1)                        # [3, 2]
+    for j in range(2):
+        if (e[0, j] + e[1, j]) + e[2, j] < 0.0:
+            e[:, j] = -e[:, j]
+    t0 = (odt[:, 0] * e[0, 0] + odt[:, 1] * e[1, 0]) + odt[:, 2] * e[2, 0]
+    t1 = (odt[:, 0] * e[0, 1] + odt[:, 1] * e[1, 1]) + odt[:, 2] * e[2, 1]
+    phi = np.arctan2(t1, t0).astype(np.float32)
+    lo, hi = stain_percentile(phi, alpha), stain_percentile(phi, 100.0 - alpha)
+    v1 = e[:, 0] * np.cos(lo) + e[:, 1] * np.sin(lo)
+    v2 = e[:, 0] * np.cos(hi) + e[:, 1] * np.sin(hi)
+    HE = np.stack([v1, v2], axis=1) if v1[0] > v2[0] else np.stack([v2, v1], axis=1)
+    a = (HE[0, 0] * HE[0, 0] + HE[1, 0] * HE[1, 0]) + HE[2, 0] * HE[2, 0]
+    b = (HE[0, 0] * HE[0, 1] + HE[1, 0] * HE[1, 1]) + HE[2, 0] * HE[2, 1]
+    d = (HE[0, 1] * HE[0, 1] + HE[1, 1] * HE[1, 1]) + HE[2, 1] * HE[2, 1]
+    det = a * d - b * b
+    if not det > STAIN_MIN_DET:
+        return row
+    P = np.stack([(d * HE[:, 0] - b * HE[:, 1]) / det, (a * HE[:, 1] - b * HE[:, 0]) / det])      # [2, 3]
+    maxc = np.zeros(2)
+    for j in range(2):
+        c = (P[j, 0] * od[:, 0] + P[j, 1] * od[:, 1]) + P[j, 2] * od[:, 2]                         # every sampled pixel, glass included
+        maxc[j] = stain_percentile(c.astype(np.float32), 99.0)
+    if not (maxc[0] > 0.0 and maxc[1] > 0.0):
+        return row
+    row[0:6], row[6:12], row[12:14], row[15] = HE.reshape(-1), P.reshape(-1), maxc, 1.0
+    return row
+
+
+def stain_fit_reference(images, pooled: bool = False, step: int = 1, Io: float = STAIN_IO, alpha: float = STAIN_ALPHA,
+                        beta: float = STAIN_BETA) -> np.ndarray:
+    """Macenko fits of uint8 [B,H,W,3] (or one [H,W,3]) over the sampled pixels -> float64 [F, 16], F = 1 if ``pooled`` else B.  A row:
+    HE [3,2] row-major (haematoxylin column first), P = (HE^T HE)^-1 HE^T [2,3], maxC [2], the tissue count n, the valid flag; an
+    invalid fit (n < 16, det(HE^T HE) not > 1e-12, a maxC not > 0) keeps n and is zero elsewhere."""
+    x = np.asarray(images)
+    px = _stain_samples(x[None] if x.ndim == 3 else x, step)
+    if pooled:
+        px = px.reshape(1, -1, 3)
+    return np.stack([_stain_fit_pixels(p, Io, alpha, beta) for p in px]) if len(px) else np.zeros((0, 16), np.float64)
+
+
+def stain_target(target=None) -> np.ndarray:
+    """float64 [8] = target HE [3,2] row-major, then target maxC [2]: None = Macenko's reference, else a fit row [16] / [1,16]"""
+    if target is None:
+        return np.concatenate([HE_REF.reshape(-1), MAXC_REF])
+    t = np.asarray(target, np.float64).reshape(-1)
+    if t.size == 16:
+        return np.concatenate([t[0:6], t[12:14]])
+    if t.size != 8:
+        raise ValueError(f"a stain target is 8 values (HE [3,2], maxC [2]) or a fit row of 16, got {t.size}")
+    return t.copy()
+
+
+def stain_apply_reference(images, fits, target=None, Io: float = STAIN_IO, unrounded: bool = False) -> np.ndarray:
+    """uint8 [B,H,W,3] normalised by ``fits`` float64 [B,16] (or [1,16] for all) to ``target`` (``stain_target``): per pixel
+    C = P . OD, C2 = C * (maxC_target / maxC), out = min(255, Io exp(-(HE_target . C2))) truncated to a byte, each operation rounded
+    once in the order written here; an image whose fit is invalid comes back unchanged.  ``unrounded``: the float64 values
+    ``Io exp(...)`` before the clip and the truncation instead -- how far a byte is from the next one (an invalid image's are its own
+    bytes)."""
+    x = np.asarray(images)
+    single = x.ndim == 3
+    x = x[None] if single else x
+    fits = np.asarray(fits, np.float64).reshape(-1, 16)
+    if x.dtype != np.uint8 or x.ndim != 4 or x.shape[3] != 3:
+        raise ValueError(f"stain images are uint8 [B,H,W,3], got {x.dtype} {tuple(x.shape)}")
+    if fits.shape[0] not in (1, x.shape[0]):
+        raise ValueError(f"need 1 or {x.shape[0]} fits, got {fits.shape[0]}")
+    tg = stain_target(target)
+    lut = stain_lut(Io)
+    out = np.empty(x.shape, np.float64)
+    for b in range(x.shape[0]):
+        f = fits[b if fits.shape[0] > 1 else 0]
+        if f[15] == 0.0:
+            out[b] = x[b]
+            continue
+        od = lut[x[b]]
+        P = f[6:12].reshape(2, 3)
+        c2 = [((P[j, 0] * od[..., 0] + P[j, 1] * od[..., 1]) + P[j, 2] * od[..., 2]) * (tg[6 + j] / f[12 + j]) for j in range(2)]
+        for ch in range(3):
+            v = np.float64(Io) * np.exp(-(tg[2 * ch] * c2[0] + tg[2 * ch + 1] * c2[1]))
+            out[b, ..., ch] = v if unrounded else np.where(v < 255.0, v, 255.0)
+    if not unrounded:
+        out = out.astype(np.uint8)
+    return out[0] if single else out
+
+
+def stain_default_step(B: int, H: int, W: int) -> int:
+    """the smallest step at which the sampled pixels of B images of H x W, B * ceil(H / step) * ceil(W / step), are at most 2^22"""
+    if B > STAIN_MAX_SAMPLES:
+        raise ValueError(f"{B} images: even one sample of each passes {STAIN_MAX_SAMPLES}")
+    step = max(1, int(np.sqrt(B * H * W / STAIN_MAX_SAMPLES)) - 1)
+    while B * (-(-H // step)) * (-(-W // step)) > STAIN_MAX_SAMPLES:
+        step += 1
+    return step
+
+
 def preprocess_images(images: Sequence, n_px: int = 224, crop: str = "torchvision") -> np.ndarray:
     return np.stack([preprocess_image(i, n_px, crop) for i in images]) if len(images) else \
         np.zeros((0, 3, n_px, n_px), np.float32)

@@ -69,10 +69,15 @@ class RegionMosaic:
 
 def encode_region(eng, region, n_px: int, projection_dim: int, crop: str, tile_px: Optional[int] = None, stride: Optional[int] = None,
                   origin=(0, 0), min_tissue: float = 0.5, sat_min: int = 18, luma_min: int = 25, luma_max: int = 235,
-                  band_rows: Optional[int] = None) -> RegionEmbeddings:
+                  band_rows: Optional[int] = None, stain=None) -> RegionEmbeddings:
     """``region`` on engine ``eng`` (tile size ``n_px``): see ``PLIP.encode_region``.  Every argument is checked before anything is
     uploaded or launched."""
     region = _as_region(region)
+    if stain is not None:
+        from .stain import StainFit, stain_apply
+        if not isinstance(stain, StainFit) or len(stain) != 1:
+            raise ValueError("stain must be a StainFit of ONE fit (PLIP.fit_stain(region, pooled=True)), got "
+                             + (f"{len(stain)} fits" if isinstance(stain, StainFit) else type(stain).__name__))
     t = int(n_px) if tile_px is None else int(tile_px)
     s = t if stride is None else int(stride)
     y0, x0 = (int(v) for v in origin)
@@ -106,6 +111,8 @@ def encode_region(eng, region, n_px: int, projection_dim: int, crop: str, tile_p
             band.record_stream(lane)
             kept.record_stream(lane)
         tiles = region_gather(e, band, kept, first, B, t, s, (0, x0))
+        if stain is not None:           # the one fit for every tile, on the gathered bytes: tissue selection has seen the raw pixels
+            tiles = stain_apply(e, tiles, stain)
         if t != n_px:
             tiles = e.resize_crop_u8(tiles, crop=crop)
         return e.encode_image_u8(tiles)
