@@ -93,9 +93,12 @@ def ln_linear(x, g, b, W, bias, eps, plan, pre=1.0, rnd=_DEFAULT):
     raise ValueError(plan)
 
 
-def _attention(qkv, B, S, H, causal, key_mask, rnd=_DEFAULT):
-    D = H * 64
-    q, k, v = (qkv[..., i * D:(i + 1) * D].reshape(B, S, H, 64).transpose(0, 2, 1, 3) for i in range(3))
+def _attention(qkv, B, S, H, causal, key_mask, rnd=_DEFAULT, probs=None):
+    """``probs``: a list that receives the fp32 probabilities [B,H,S,S] of the rounded q/k/v -- what the engine's attention_probs
+    kernel computes from its qkv buffer (masked entries exactly 0)"""
+    D = qkv.shape[-1] // 3
+    dh = D // H                     # the head size is the tower's width // heads (64 for every OpenAI CLIP, 80 / 88 for ViT-H / -g)
+    q, k, v = (qkv[..., i * D:(i + 1) * D].reshape(B, S, H, dh).transpose(0, 2, 1, 3) for i in range(3))
     s = (q.astype(np.float64) @ k.astype(np.float64).transpose(0, 1, 3, 2)).astype(np.float32)   # scale folded into q
     neg = np.float32(-1e30)
     if causal:
@@ -103,34 +106,40 @@ def _attention(qkv, B, S, H, causal, key_mask, rnd=_DEFAULT):
     if key_mask is not None:
         s = np.where(np.asarray(key_mask, bool)[:, None, None, :], s, neg)
     p = np.exp(s - s.max(-1, keepdims=True))
+    if probs is not None:
+        probs.append(p / p.sum(-1, keepdims=True))
     o = (rnd("p", p).astype(np.float64) @ v.astype(np.float64)).astype(np.float32) / p.sum(-1, keepdims=True)
     return rnd("att", o.transpose(0, 2, 1, 3).reshape(B, S, D))
 
 
-def _layers(x, sd, prefix, L, H, causal, key_mask, eps, plan, hidden, rnd=_DEFAULT, lead=0):
+def _layers(x, sd, prefix, L, H, causal, key_mask, eps, plan, hidden, rnd=_DEFAULT, lead=0, act="quick_gelu", probs=None):
     """``lead``: the first ``lead`` blocks round their operands to f16 whatever ``rnd`` says for the rest
-    (plipmi_config.text_f16_layers: a bf16 text tower whose leading blocks run on IEEE-half operands)."""
+    (plipmi_config.text_f16_layers: a bf16 text tower whose leading blocks run on IEEE-half operands).
+    ``act``: the tower's ``hidden_act`` (oracle.clip_oracle.ACTIVATIONS); ``probs``: receives every block's probabilities."""
     B, S, D = x.shape
+    act = O.activation(act)
+    q_scale = float(D // H) ** -0.5           # 1/8 for 64-wide heads, folded into W_q and b_q
     rnd_rest, rnd_lead = rnd, Rounding("f16", rnd.sites)
     for i in range(L):
         rnd = rnd_lead if i < lead else rnd_rest
         p = f"{prefix}.encoder.layers.{i}"
         g1, b1 = _f(sd, f"{p}.layer_norm1.weight"), _f(sd, f"{p}.layer_norm1.bias")
         parts = []
-        for name, pre in (("q_proj", 0.125), ("k_proj", 1.0), ("v_proj", 1.0)):
+        for name, pre in (("q_proj", q_scale), ("k_proj", 1.0), ("v_proj", 1.0)):
             parts.append(ln_linear(x, g1, b1, _f(sd, f"{p}.self_attn.{name}.weight"), _f(sd, f"{p}.self_attn.{name}.bias"),
                                    eps, plan, pre, rnd))
         qkv = rnd("qkv", np.concatenate(parts, axis=-1))
-        att = _attention(qkv, B, S, H, causal, key_mask, rnd)
+        att = _attention(qkv, B, S, H, causal, key_mask, rnd, probs)
         x = x + (_mm(att, rnd("w", _f(sd, f"{p}.self_attn.out_proj.weight"))) + _f(sd, f"{p}.self_attn.out_proj.bias"))
         g2, b2 = _f(sd, f"{p}.layer_norm2.weight"), _f(sd, f"{p}.layer_norm2.bias")
-        m = rnd("mlp", O.quick_gelu(ln_linear(x, g2, b2, _f(sd, f"{p}.mlp.fc1.weight"), _f(sd, f"{p}.mlp.fc1.bias"), eps, plan, 1.0, rnd)))
+        m = rnd("mlp", act(ln_linear(x, g2, b2, _f(sd, f"{p}.mlp.fc1.weight"), _f(sd, f"{p}.mlp.fc1.bias"), eps, plan, 1.0, rnd)))
         x = x + (_mm(m, rnd("w", _f(sd, f"{p}.mlp.fc2.weight"))) + _f(sd, f"{p}.mlp.fc2.bias"))
         hidden.append(x)
     return x
 
 
-def vision_tower(pixels, sd, cfg, plan="folded", return_hidden=False, dtype="bf16", sites=ALL_SITES):
+def vision_outputs(pixels, sd, cfg, plan="folded", dtype="bf16", sites=ALL_SITES, attentions=False):
+    """every field of the vision tower under the plan, named as ``oracle.clip_oracle.vision_outputs`` names them"""
     rnd = Rounding(dtype, sites)
     pixels = np.asarray(pixels, np.float32)
     B, Dv = pixels.shape[0], cfg.v_width
@@ -141,28 +150,42 @@ def vision_tower(pixels, sd, cfg, plan="folded", return_hidden=False, dtype="bf1
     x = O.layer_norm(x, _f(sd, "vision_model.pre_layrnorm.weight"), _f(sd, "vision_model.pre_layrnorm.bias"),
                      cfg.layer_norm_eps)
     hidden = [x]
-    x = _layers(x, sd, "vision_model", cfg.v_layers, cfg.v_heads, False, None, cfg.layer_norm_eps, plan, hidden, rnd)
+    probs = [] if attentions else None
+    x = _layers(x, sd, "vision_model", cfg.v_layers, cfg.v_heads, False, None, cfg.layer_norm_eps, plan, hidden, rnd,
+                act=cfg.v_hidden_act, probs=probs)
     pooled = O.layer_norm(x[:, 0, :], _f(sd, "vision_model.post_layernorm.weight"),
                           _f(sd, "vision_model.post_layernorm.bias"), cfg.layer_norm_eps)
     emb = pooled @ _f(sd, "visual_projection.weight").T
-    return (emb, hidden) if return_hidden else emb
+    return {"image_features": emb, "pooler_output": pooled, "last_hidden_state": x, "hidden_states": hidden, "attentions": probs}
 
 
-def text_tower(ids, sd, cfg, attention_mask=None, plan="folded", return_hidden=False, dtype="bf16", sites=ALL_SITES,
-               lead_f16=0):
+def vision_tower(pixels, sd, cfg, plan="folded", return_hidden=False, dtype="bf16", sites=ALL_SITES):
+    out = vision_outputs(pixels, sd, cfg, plan, dtype, sites)
+    return (out["image_features"], out["hidden_states"]) if return_hidden else out["image_features"]
+
+
+def text_outputs(ids, sd, cfg, attention_mask=None, plan="folded", dtype="bf16", sites=ALL_SITES, lead_f16=0, attentions=False):
+    """every field of the text tower under the plan, named as ``oracle.clip_oracle.text_outputs`` names them"""
     rnd = Rounding(dtype, sites)
     ids = np.asarray(ids)
     B, S = ids.shape
     x = _f(sd, "text_model.embeddings.token_embedding.weight")[ids] + \
         _f(sd, "text_model.embeddings.position_embedding.weight")[None, :S]
     hidden = [x]
+    probs = [] if attentions else None
     x = _layers(x, sd, "text_model", cfg.t_layers, cfg.t_heads, True, attention_mask, cfg.layer_norm_eps, plan, hidden, rnd,
-                lead_f16)
+                lead_f16, act=cfg.t_hidden_act, probs=probs)
     x = O.layer_norm(x, _f(sd, "text_model.final_layer_norm.weight"), _f(sd, "text_model.final_layer_norm.bias"),
                      cfg.layer_norm_eps)
     pooled = x[np.arange(B), O.eos_positions(ids, cfg.eos_token_id)]
     emb = pooled @ _f(sd, "text_projection.weight").T
-    return (emb, hidden) if return_hidden else emb
+    return {"text_features": emb, "pooler_output": pooled, "last_hidden_state": x, "hidden_states": hidden, "attentions": probs}
+
+
+def text_tower(ids, sd, cfg, attention_mask=None, plan="folded", return_hidden=False, dtype="bf16", sites=ALL_SITES,
+               lead_f16=0):
+    out = text_outputs(ids, sd, cfg, attention_mask, plan, dtype, sites, lead_f16)
+    return (out["text_features"], out["hidden_states"]) if return_hidden else out["text_features"]
 
 
 def clip_forward(pixels, ids, sd, cfg, attention_mask=None, plan="folded", dtype="bf16", sites=ALL_SITES):

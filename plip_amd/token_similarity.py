@@ -16,11 +16,14 @@ def token_similarity(engine, pixels: torch.Tensor, text_embeds: torch.Tensor, sc
     """``similarity`` [B,S,C] = scale * cosine(E[b,s], text_embeds[c]) with E = visual_projection(post_layernorm(last_hidden_state)) on
     every token of ``pixels`` (fp32 [B,3,H,W] at the engine's image size; row 0 = CLS, then the patch grid row-major), or with
     ``softmax`` its softmax over the C text rows; ``return_embeds``: also ``token_embeds`` [B,S,P], E itself.  ``text_embeds`` [C,P]
-    float, rows of any norm (what ``encode_text(..., normalize=False)`` returns will do), 1 <= C <= 64.  fp32 on the GPU; runs in chunks
+    float, rows of any norm (what ``encode_text(..., normalize=False)`` returns will do), 1 <= C <= 64; a model whose ``projection_dim``
+    is no multiple of 32 is refused with ValueError (the per-token projection has no kernel for it).  fp32 on the GPU; runs in chunks
     of ``max_batch`` images.  Raises ValueError before allocating anything when outputs and scratch would not fit the device's free
     memory."""
     code, (S, D, H, L), B, chunks = engine._tower_input_check("vision", pixels, None)
     P = engine.cfg.projection_dim
+    if P % 32:      # refused here as in the C entry, before anything is allocated or launched: there is no kernel for such a head
+        raise ValueError(f"projection_dim = {P}: the per-token head takes multiples of 32 (the encode paths take any width)")
     if not torch.is_tensor(text_embeds):
         text_embeds = torch.as_tensor(text_embeds)
     if text_embeds.dim() != 2 or text_embeds.shape[1] != P or not text_embeds.is_floating_point():

@@ -299,6 +299,33 @@ def test_softmax_and_errors(engines, golden, monkeypatch):
         token_similarity(eng, pix, T)
 
 
+@pytest.mark.parametrize("P", [80, 200])
+def test_projection_widths_without_a_kernel_are_refused_by_name(P):
+    """a projection_dim that is no multiple of 32 encodes (head_gemm takes any width) but has no per-token head: Python refuses before
+    anything is allocated, the C entry before anything is launched, both by name; the encode paths of the same engine still run"""
+    from plip_amd.config import get_config
+    from plip_amd.model import PlipModel
+    from plip_amd.token_similarity import token_similarity
+    model = PlipModel.from_synthetic(get_config("tiny").replace(projection_dim=P), seed=3, dtype="bf16", max_batch=2)
+    eng = model.engine
+    try:
+        pix = torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(P))
+        with pytest.raises(ValueError, match=f"projection_dim = {P}.*multiples of 32"):
+            token_similarity(eng, pix, torch.randn(3, P))
+        with pytest.raises(ValueError, match="multiples of 32"):
+            model.vision_model.token_similarity(pix, torch.randn(3, P))
+        x, t = pix.to(DEV), torch.randn(3, P).to(DEV)
+        out = torch.full((2, 17, 3), -7.5, device=DEV)
+        rc = eng.lib.plipmi_encode_token_similarity(eng._h, C.c_void_p(x.data_ptr()), 2, C.c_void_p(t.data_ptr()), 3, 1.0, 0, None,
+                                                    C.c_void_p(out.data_ptr()), eng._stream())
+        assert rc == 1 and f"projection_dim = {P}" in _lib.last_error() and "multiples of 32" in _lib.last_error()
+        torch.cuda.synchronize()
+        assert (out == -7.5).all()
+        assert torch.isfinite(eng.encode_image(pix, normalize=True)).all()
+    finally:
+        eng.close()
+
+
 def test_plip_similarity_maps(engines, golden):
     """three native-size uint8 tiles of the tiny model against six prompts: [3, 6, 4, 4] maps = the engine's scores on the pixels
     encode_images encodes, CLS dropped; token ids and a ready [C, P] array give the same maps; image_size= runs on the resolution handle"""

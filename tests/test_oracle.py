@@ -302,3 +302,225 @@ def test_config3_zero_shot_fixture_is_the_reference_head(golden):
     np.testing.assert_array_equal(g["scores"].argmax(1), g["argmax"])
     hist = np.bincount(g["argmax"], minlength=10)
     assert (hist >= n // 25).sum() >= 5, hist
+
+
+# ---- the oracle at the product's surface: activations, head sizes, resolutions, per-token outputs, token similarity ----------------
+# Every committed HF fixture of those features against the extended oracle, under the f32 rows the fixtures' own GPU tests apply
+# (tests/test_gpu_parity.py TOL, tests/test_gpu_tower_outputs.py TOL, tests/test_gpu_token_similarity.py HF_TOL and its caps,
+# tests/test_gpu_attention_summary.py ROLLOUT_TOL and its cap).  The oracle runs in float32 unless a test says otherwise.
+import hashlib  # noqa: E402
+import os  # noqa: E402
+import sys  # noqa: E402
+
+_TOOLS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
+if _TOOLS not in sys.path:
+    sys.path.insert(0, _TOOLS)
+
+from attention_summary_refs import rollout_ref  # noqa: E402
+from test_gpu_attention_summary import ROLLOUT_TOL  # noqa: E402
+from test_gpu_parity import TOL as PARITY_TOL  # noqa: E402
+from test_gpu_token_similarity import HF_TOL as SIM_TOL  # noqa: E402
+from test_gpu_tower_outputs import TOL as TOWER_TOL  # noqa: E402
+
+F32 = PARITY_TOL["f32"]
+
+
+def _pair_fields(tag, o, g, sd, keys=("image_features", "text_features", "image_embeds", "text_embeds", "logits_per_image")):
+    kind = {"image_features": "feat", "text_features": "feat", "image_embeds": "emb", "text_embeds": "emb", "logits_per_image": "cos"}
+    for k in keys:
+        div = np.exp(np.float64(sd["logit_scale"])) if k == "logits_per_image" else 1.0
+        err = float(np.abs(o[k].astype(np.float64) - g[k]).max() / div)
+        print(f"oracle vs HF {tag} {k}: {err:.2e} (bound {F32[kind[k]]:.1e})")
+        assert err <= F32[kind[k]], (tag, k, err)
+
+
+def test_defaults_give_the_bits_of_the_parent_oracle():
+    """every call the oracle had before it learnt activations, resolutions and per-token outputs returns the same bits: sha256 over
+    clip_forward, both towers with hidden states and the unmasked text tower of tiny_b6, float32 and float64, and over the
+    precision model's three plans -- the digests are of the arrays the previous version of these modules returned"""
+    from oracle import precision_model as P
+    cfg, sd, px, ids, mask = case_inputs("tiny_b6")
+    h = hashlib.sha256()
+    for dt in (np.float32, np.float64):
+        o = O.clip_forward(px, ids, sd, cfg, mask, dtype=dt)
+        for k in sorted(o):
+            h.update(np.ascontiguousarray(o[k]).tobytes())
+        e, vh = O.vision_tower(px, sd, cfg, dt, return_hidden=True)
+        h.update(e.tobytes())
+        h.update(np.stack(vh).tobytes())
+        e, th = O.text_tower(ids, sd, cfg, mask, dt, return_hidden=True)
+        h.update(e.tobytes())
+        h.update(np.stack(th).tobytes())
+        h.update(O.text_tower(ids, sd, cfg, None, dt).tobytes())
+    assert h.hexdigest() == "d0f5b3bbd69fc45c7d1334aad3a6a3268fd77855ceb6fbef0227a266ad7e5053"
+    h = hashlib.sha256()
+    for dt, plan in (("bf16", "folded"), ("f16", "folded"), ("bf16", "round_ln")):
+        o = P.clip_forward(px, ids, sd, cfg, mask, plan, dtype=dt)
+        for k in sorted(o):
+            h.update(np.ascontiguousarray(o[k]).tobytes())
+    e, th = P.text_tower(ids, sd, cfg, mask, return_hidden=True, lead_f16=1)
+    h.update(e.tobytes())
+    h.update(np.stack(th).tobytes())
+    assert h.hexdigest() == "949613712008f2be0c97f23d0fd2b8ed704cc6c06a9e99644ab5be01d204f49e"
+
+
+def test_gelu_is_the_erf_form():
+    import math
+    x = np.linspace(-6, 6, 241).astype(np.float32)
+    want = np.array([0.5 * float(v) * (1.0 + math.erf(float(v) / math.sqrt(2.0))) for v in x])
+    assert np.abs(O.gelu(x).astype(np.float64) - want).max() <= 2.0 ** -24 * 6
+    assert O.gelu(x).dtype == np.float32 and O.gelu(x.astype(np.float64)).dtype == np.float64
+    with pytest.raises(ValueError, match="hidden_act"):
+        O.activation("gelu_new")
+
+
+@pytest.mark.parametrize("name,v_act,t_act", [("gelu_tiny_b6", "gelu", "gelu"), ("gelu_tiny_b6_vision", "gelu", "quick_gelu"),
+                                              ("gelu_tiny_b6_text", "quick_gelu", "gelu")])
+def test_oracle_matches_hf_gelu_towers(name, v_act, t_act, golden):
+    g = golden(name)
+    cfg, sd, px, ids, mask = case_inputs("tiny_b6")
+    cfg = cfg.replace(v_hidden_act=v_act, t_hidden_act=t_act)
+    _pair_fields(name, O.clip_forward(px, ids, sd, cfg, mask), g, sd)
+    if "vision_hidden" in g:
+        _, vh = O.vision_tower(px, sd, cfg, return_hidden=True)
+        _, th = O.text_tower(ids, sd, cfg, mask, return_hidden=True)
+        assert np.abs(np.stack(vh) - g["vision_hidden"]).max() <= F32["hidden"]
+        assert np.abs((np.stack(th) - g["text_hidden"]) * mask[None, :, :, None]).max() <= F32["hidden"]
+    # the fixture separates the activations: the quick_gelu oracle misses the same bound on a field of each gelu tower
+    q = O.clip_forward(px, ids, sd, cfg.replace(v_hidden_act="quick_gelu", t_hidden_act="quick_gelu"), mask)
+    for tower, act in (("image", v_act), ("text", t_act)):
+        assert (np.abs(q[f"{tower}_features"] - g[f"{tower}_features"]).max() > 30 * F32["feat"]) == (act == "gelu")
+
+
+def test_oracle_matches_hf_gelu_at_144x128(golden):
+    g = golden("gelu_tiny_144x128")
+    cfg, sd, *_ = case_inputs("tiny_b6")
+    cfg = cfg.replace(v_hidden_act="gelu", t_hidden_act="gelu")
+    px = np.random.RandomState(int(g["seed"])).standard_normal(tuple(int(v) for v in g["shape"])).astype(np.float32)
+    got = O.vision_tower(px, sd, cfg, image_hw=px.shape[2:])
+    err = float(np.abs(got - g["image_features"]).max())
+    print(f"oracle vs HF gelu 144x128 image_features: {err:.2e}")
+    assert err <= F32["feat"]
+
+
+@pytest.mark.parametrize("name", ["hd80", "hd88_p4", "text80", "hd128"])
+def test_oracle_matches_hf_head_sizes(name, golden):
+    import make_head_dim_golden as M
+    g = golden(f"head_dim_{name}")
+    cfg, sd, px, ids, mask = M.case_inputs(name)
+    _pair_fields(name, O.clip_forward(px, ids, sd, cfg, mask), g, sd)
+    _, vh = O.vision_tower(px, sd, cfg, return_hidden=True)
+    vh = np.stack(vh)
+    for key, rows in (("vision_hidden", vh), ("vision_hidden_cls", vh[:, :, 0]), ("vision_hidden_last_token", vh[:, :, -1])):
+        if key in g:
+            assert np.abs(rows - g[key]).max() <= F32["hidden"], (name, key)
+    if "text_hidden" in g:
+        _, th = O.text_tower(ids, sd, cfg, mask, return_hidden=True)
+        assert np.abs((np.stack(th) - g["text_hidden"]) * mask[None, :, :, None]).max() <= F32["hidden"]
+    if "res96/image_features" in g:
+        got = O.vision_tower(M.res_pixels(), sd, cfg, image_hw=M.RES_HW)
+        err = float(np.abs(got - g["res96/image_features"]).max())
+        print(f"oracle vs HF {name} res96/image_features: {err:.2e}")
+        assert err <= F32["feat"]
+
+
+@pytest.mark.parametrize("size", ["448x448", "288x256", "250x250", "230x224", "160x160"])
+def test_oracle_matches_hf_at_other_resolutions(size, golden):
+    """ViT-B/32 with interpolate_pos_encoding=True: up- and down-scaled grids, a non-square one, a size that is no multiple of the
+    patch (the grid floors; HF keeps its own table on the square 7 x 7) and 7 x 7 on a non-square image (resampled 7 -> 7)"""
+    g = golden("vitb32_b4_resolutions")
+    cfg, sd, _, ids, mask = case_inputs("vitb32_b4")
+    shape = tuple(int(v) for v in g[f"{size}/shape"])
+    px = np.random.RandomState(int(g[f"{size}/seed"])).standard_normal(shape).astype(np.float32)
+    o = O.clip_forward(px, ids, sd, cfg, mask, image_hw=shape[2:])
+    _pair_fields(size, o, {k: g[f"{size}/{k}"] for k in ("image_features", "image_embeds", "logits_per_image")}, sd,
+                 ("image_features", "image_embeds", "logits_per_image"))
+
+
+def _tower_fields(tag, out, g, prefix, tower):
+    """tests/test_gpu_tower_outputs.py _compare on the oracle's fields: hid / last / pool relative to the field's largest magnitude,
+    attn absolute"""
+    t = TOWER_TOL["f32"]
+    rel = lambda a, b: float(np.abs(np.asarray(a, np.float64) - b).max() / np.abs(b).max())
+    errs = {"last": rel(out["last_hidden_state"], g[f"{prefix}/{tower}_last_hidden_state"]),
+            "pool": rel(out["pooler_output"], g[f"{prefix}/{tower}_pooler_output"]),
+            "hid": max(rel(out["hidden_states"][int(i)], g[f"{prefix}/{tower}_hidden_states"][k])
+                       for k, i in enumerate(g[f"{prefix}/{tower}_hidden_idx"])),
+            "attn": max(float(np.abs(np.asarray(out["attentions"][int(i)], np.float64) - g[f"{prefix}/{tower}_attentions"][k]).max())
+                        for k, i in enumerate(g[f"{prefix}/{tower}_attn_idx"]))}
+    print(f"oracle vs HF tower outputs {tag} {tower}: " + " ".join(f"{k} {v:.2e} (bound {t[k]:.1e})" for k, v in errs.items()))
+    for k, v in errs.items():
+        assert v <= t[k], (tag, tower, k, v, t[k])
+
+
+def _masked_entries_are_zero(att, mask, causal):
+    for a in att:
+        B, H, S, _ = a.shape
+        dead = np.zeros((B, S, S), bool)
+        if causal:
+            dead |= np.triu(np.ones((S, S), bool), 1)[None]
+        if mask is not None:
+            dead |= (np.asarray(mask) == 0)[:, None, :]
+        assert (a[np.broadcast_to(dead[:, None], a.shape)] == 0.0).all()
+        np.testing.assert_allclose(a.sum(-1), 1.0, atol=1e-5, rtol=0)
+
+
+def test_oracle_matches_hf_tower_outputs_tiny(golden):
+    """every hidden state and attention map of both towers, last_hidden_state and pooler_output: captions under their mask, without
+    one, and zero-padded captions (argmax pooling)"""
+    g = golden("tower_outputs_tiny")
+    cfg, sd, px, ids, mask = case_inputs("tiny_b6")
+    _tower_fields("tiny", O.vision_outputs(px, sd, cfg, attentions=True), g, "eos_masked", "vision")
+    t = O.text_outputs(ids, sd, cfg, mask, attentions=True)
+    _tower_fields("tiny masked", t, g, "eos_masked", "text")
+    _masked_entries_are_zero(t["attentions"], mask, True)
+    t = O.text_outputs(ids, sd, cfg, None, attentions=True)
+    _tower_fields("tiny unmasked", t, g, "eos_nomask", "text")
+    _masked_entries_are_zero(t["attentions"], None, True)
+    cfg, sd, px, ids, mask = case_inputs("tiny_b5_zero_pad_ln100")
+    _tower_fields("tiny zero-pad", O.text_outputs(ids, sd, cfg, None, attentions=True), g, "zero", "text")
+    # the tuple forms of the towers carry the same arrays
+    emb, hid, att = O.text_tower(ids, sd, cfg, None, return_hidden=True, return_attentions=True)
+    assert len(hid) == cfg.t_layers + 1 and len(att) == cfg.t_layers and att[0].shape == (5, cfg.t_heads, 16, 16)
+    emb2, att2 = O.vision_tower(px, sd, cfg, return_attentions=True)
+    assert emb2.shape == (5, cfg.projection_dim) and len(att2) == cfg.v_layers
+
+
+def test_oracle_matches_hf_token_similarity_tiny(golden):
+    g = golden("token_similarity_tiny")
+    cfg, sd, px, ids, mask = case_inputs("tiny_b6")
+    T = golden("tiny_b6")["text_embeds"]
+    last = O.vision_outputs(px, sd, cfg)["last_hidden_state"]
+    E, s = O.token_similarity(last, sd, cfg, T)
+    emax = float(np.abs(g["token_embeds"]).max())
+    err_e = float(np.abs(E.astype(np.float64) - g["token_embeds"]).max()) / emax
+    err_s = float(np.abs(s.astype(np.float64) - g["similarity"]).max())
+    cap_e = 0.1 * float(g["token_embeds"].astype(np.float64).std()) / emax
+    cap_s = 0.1 * float(g["similarity"][:, 1:].astype(np.float64).std())
+    print(f"oracle vs HF token similarity: token_embeds {err_e:.2e}, similarity {err_s:.2e}")
+    assert err_e <= min(SIM_TOL["embeds"]["f32"], cap_e) and err_s <= min(SIM_TOL["similarity"]["f32"], cap_s)
+    # text rows of any norm give the same scores; the scale multiplies them; softmax runs over the prompts
+    scaled = T * np.logspace(-2, 2, T.shape[0], dtype=np.float32)[:, None]
+    assert np.abs(O.token_similarity(last, sd, cfg, scaled)[1] - s).max() <= 4 * 2.0 ** -24
+    s100 = O.token_similarity(last, sd, cfg, T, scale=100.0, dtype=np.float64)[1]
+    sm = O.token_similarity(last, sd, cfg, T, scale=100.0, softmax=True, dtype=np.float64)[1]
+    e = np.exp(s100 - s100.max(-1, keepdims=True))
+    np.testing.assert_allclose(sm, e / e.sum(-1, keepdims=True), rtol=0, atol=1e-15)
+    # row 0 is the pooled row: its scores are the pair's cosines
+    assert np.abs(s[:, 0] - golden("tiny_b6")["image_embeds"] @ T.T).max() <= F32["cos"]
+
+
+def test_oracle_matches_hf_attention_summary_tinyp4(golden):
+    """257 vision tokens: the pooled rows of every block and the rollout (tests/attention_summary_refs.rollout_ref on the oracle's
+    probabilities) against HF's"""
+    g = golden("attention_summary_tinyp4")
+    cfg, sd, px, ids, mask = case_inputs("tinyp4_b3")
+    att = O.vision_outputs(px, sd, cfg, attentions=True)["attentions"]
+    L = len(att)
+    e_pool = max(float(np.abs(att[l][:, :, 0, :].astype(np.float64) - g["vision_pooled_attention"][l]).max()) for l in range(L))
+    R = rollout_ref(att)
+    e_mat = float(np.abs(R - g["vision_rollout_matrix"]).max())
+    e_row = float(np.abs(R[:, 0] - g["vision_rollout"]).max())
+    print(f"oracle vs HF attention summary tinyp4: pooled {e_pool:.2e} rollout_matrix {e_mat:.2e} rollout {e_row:.2e}")
+    assert e_pool <= TOWER_TOL["f32"]["attn"]
+    assert max(e_mat, e_row) <= min(ROLLOUT_TOL["f32"], L * TOWER_TOL["f32"]["attn"])
