@@ -602,6 +602,49 @@ int plipmi_stain_apply(plipmi_handle h, const uint8_t* src, int B, int H, int W,
                        const double* fits, int n_fits, const double* target_dev, double Io, const double* lut_dev, uint8_t* dst,
                        void* stream);
 
+/* ---- bags of embeddings: slide-level top-K pooling and bag means ----------------
+ * (Additive, like the entries above it: the version number and every existing entry are unchanged; a caller probes for the symbols.)
+ * A BAG is a contiguous row range of X fp32 [N, D] (device, 16-byte aligned, D % 4 == 0, 4 <= D <= 1024): bag b is rows
+ * [offsets[b], offsets[b + 1]), offsets int32 [S + 1] on the device, non-decreasing, offsets[0] = 0, offsets[S] = N; empty bags are
+ * allowed.  The C entries cannot see the contents of offsets: the kernels clamp what they read to [0, N] and to non-decreasing values, so
+ * no access leaves X or the outputs whatever the array holds (rows that then belong to no bag are ignored); the Python layer validates
+ * them.  The definition is the project's own (tests/bags_common.py is its numpy statement; csrc/bags.hip):
+ *   scores    s[c, i] = scale * (x_i . t_c) for T fp32 [C, D] (device, 16-byte aligned), 1 <= C <= PLIPMI_BAG_MAX_CLASSES; rows are used
+ *             as given (unit rows for cosine).  Exact-fp32 MFMA products, the same tile and the same per-row order of the columns for
+ *             every row: a row's score bits do not depend on N, on its bag or on the other bags of the call.  Class-major [C, N].
+ *   order     (v, i) ranks before (w, j) iff v > w, or v == w and i < j (ties go to the lower row); -0.0 and +0.0 are equal; a NaN
+ *             score counts as -inf.
+ *   pooling   ks: 1 .. PLIPMI_BAG_MAX_KS strictly ascending values in 1 .. PLIPMI_BAG_MAX_K on the HOST, kmax = the last.  For bag b of
+ *             n_b rows, class c and k, m = min(k, n_b):  pooled[b, j, c] = (float)(the sum of the m first-ranked scores / (double)m),
+ *             the sum in float64 rank by rank (first-ranked first); NaN for an empty bag.
+ *             The selection is exact.
+ *   pred      pred[b, j] = the first arg-max over c of pooled[b, j, :] (a NaN never wins over a number); -1 for an empty bag.
+ *   top_idx   top_idx[b, c, r] = the row of X (int32) of rank r < min(kmax, n_b), -1 beyond; an index written lies inside its bag.
+ *   mean      mean[b, :] = (float)(the float64 sum of the bag's rows / n_b), the sum in a fixed association of ascending rows; with
+ *             normalize, that fp32 row divided by its norm (float64); zeros for an empty bag or a zero norm.
+ * No floating-point atomics, every sum in a fixed order: the same inputs give the same bits on every run.
+ * plipmi_bag_topk_pool: the score pass, then the pooling of those scores; scores_out (fp32 [C, N], may be NULL) keeps them.
+ * plipmi_bag_pool_scores: the same pooling of any class-major per-tile scores scoresT [C, ld], ld >= N -- the transposed output of
+ * plipmi_logits, a probe's decision values.  pooled fp32 [S, nks, C]; pred int32 [S, nks] and top_idx int32 [S, C, kmax] may be NULL.
+ * plipmi_bag_mean: mean fp32 [S, D].
+ * All three only enqueue: no synchronisation, no allocation, no host work per bag, and a grid that depends on N, S, C alone (bag sizes
+ * are read on the device), so the calls can be captured in a graph.  workspace: plipmi_bag_workspace bytes of the caller's (for
+ * plipmi_bag_mean those of C = 1, kmax = 1 suffice), 16-byte aligned; it holds nothing between calls.
+ * PLIPMI_ERR_INVALID with a message that names the limit, before any launch: a null required pointer, S < 1, C outside 1 .. 64, nks
+ * outside 1 .. 8, a k outside 1 .. 1024, ks not strictly ascending, ld < N, a misaligned X, T or workspace, N < 1, D % 4, D outside
+ * 4 .. 1024. */
+#define PLIPMI_BAG_MAX_K 1024
+#define PLIPMI_BAG_MAX_KS 8
+#define PLIPMI_BAG_MAX_CLASSES 64
+size_t plipmi_bag_workspace(int N, int S, int C, int kmax);   /* 0 for sizes the entries refuse */
+int plipmi_bag_topk_pool(plipmi_handle h, const float* X, int N, int D, const int32_t* offsets, int S, const float* T, int C, float scale,
+                         const int32_t* ks_host, int nks, void* workspace, float* pooled /*[S,nks,C]*/, int32_t* pred /*[S,nks] or NULL*/,
+                         int32_t* top_idx /*[S,C,kmax] or NULL*/, float* scores_out /*[C,N] or NULL*/, void* stream);
+int plipmi_bag_pool_scores(plipmi_handle h, const float* scoresT, int64_t ld, int N, int C, const int32_t* offsets, int S,
+                           const int32_t* ks_host, int nks, void* workspace, float* pooled, int32_t* pred, int32_t* top_idx, void* stream);
+int plipmi_bag_mean(plipmi_handle h, const float* X, int N, int D, const int32_t* offsets, int S, int normalize, void* workspace,
+                    float* mean /*[S,D]*/, void* stream);
+
 /* ---- measurement ------------------------------------------------------------
  * (kernel-level test entries and A/B hooks live in plipmi_test.h: same library, not part of the product interface) */
 /* Per-kernel timing with HIP events recorded on the launch stream.  While

@@ -84,6 +84,8 @@ class KMeansInfo(C.Structure):
                 ("inertia", C.c_double), ("center_shift", C.c_double)]
 
 
+BAG_MAX_K, BAG_MAX_KS, BAG_MAX_CLASSES = 1024, 8, 64    # include/plipmi.h PLIPMI_BAG_MAX_K / _KS / _CLASSES
+
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 # kernel-level test entries and A/B hooks (include/plipmi_test.h): tests/, tools/ and bench.py's side fields only
 TEST_SYMBOLS = {
@@ -172,6 +174,10 @@ SYMBOLS = {
     "plipmi_stain_workspace": (C.c_size_t, [_i, _i, _i, _i]),
     "plipmi_stain_fit": (_i, [_vp, _vp, _i, _i, _i, C.c_int64, C.c_int64, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
     "plipmi_stain_apply": (_i, [_vp, _vp, _i, _i, _i, C.c_int64, C.c_int64, _vp, _i, _vp, C.c_double, _vp, _vp, _vp]),
+    "plipmi_bag_workspace": (C.c_size_t, [_i, _i, _i, _i]),
+    "plipmi_bag_topk_pool": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _f, C.POINTER(C.c_int32), _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plipmi_bag_pool_scores": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, _i, C.POINTER(C.c_int32), _i, _vp, _vp, _vp, _vp, _vp]),
+    "plipmi_bag_mean": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "plipmi_profile_enable": (_i, [_vp, _i]),
     "plipmi_profile_read": (_i, [_vp, C.POINTER(KernelStat), _i, C.POINTER(_i)]),
 }

@@ -39,6 +39,8 @@ LATER_SOURCES = ["kmeans.hip"]
 # LATER_SOURCES is closed too (tests/test_kmeans_host.py pins its tail); what comes after it goes here, under the same rule.
 # Macenko stain normalisation (moments, basis, keys, the exact percentile's radix select, apply) and its entries
 STAIN_SOURCES = ["stain.hip"]
+# STAIN_SOURCES is closed too (tests/test_stain_host.py pins it).  Bags of embeddings (slide-level top-K pooling, bag means) and their entries
+BAG_SOURCES = ["bags.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-Wno-unused-value"]
 
@@ -91,7 +93,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     hdr_digest = _digest(headers)
     jobs = []
     objs = []
-    for src in SOURCES + LATER_SOURCES + STAIN_SOURCES:
+    for src in SOURCES + LATER_SOURCES + STAIN_SOURCES + BAG_SOURCES:
         obj = os.path.join(BUILD, src.replace(".hip", ".o"))
         stamp = obj + ".sha"
         want = _digest([os.path.join(CSRC, src)]) + hdr_digest

@@ -287,6 +287,72 @@ class PLIP:
         reps = res.representatives.cpu().numpy().astype(np.int64)
         return RegionMosaic(reg, reps, reg.coords[reps], reg.kept[reps], res.labels.cpu().numpy(), res.counts.cpu().numpy(), res)
 
+    def class_prototypes(self, classes, templates=("{}",), batch_size: int = 256) -> np.ndarray:
+        """(extension) One text prototype per class, float32 [C, P] unit rows: the L2-normalised mean of the L2-normalised
+        ``encode_text`` embeddings of every template x synonym -- CLIP's ``zeroshot_classifier`` (prompt ensembling).  ``classes``: a
+        list of names, or a list of lists of synonyms; ``templates``: format strings with one ``{}``."""
+        from .bags import class_prototypes
+        names = [[c] if isinstance(c, str) else list(c) for c in classes]
+        templates = [templates] if isinstance(templates, str) else list(templates)
+        if not names or not templates or any(not n for n in names):
+            raise ValueError("class_prototypes: need at least one class, one name per class and one template")
+        prompts, groups = [], []
+        for syn in names:
+            groups.append(list(range(len(prompts), len(prompts) + len(syn) * len(templates))))
+            prompts.extend(t.format(s) for s in syn for t in templates)
+        return class_prototypes(self.encode_text(prompts, batch_size=batch_size), groups)
+
+    def _prototypes(self, classes_or_prototypes, templates):
+        c = classes_or_prototypes
+        if torch.is_tensor(c) or isinstance(c, np.ndarray):
+            return c
+        return self.class_prototypes(c, templates=templates)
+
+    def slide_zero_shot(self, bags, classes_or_prototypes, ks=(1, 5, 10, 50, 100), templates=("{}",), scale: Optional[float] = None,
+                        return_top_tiles: int = 0) -> dict:
+        """(extension) Slide-level zero-shot by top-K pooling (MI-Zero, CONCH) on the GPU (bags.py; include/plipmi.h "bags of
+        embeddings"): every tile of every slide is scored against every class prototype, the ``k`` largest scores of a slide and class
+        are averaged for every ``k`` of ``ks``, and the slide's prediction is the first arg-max over the classes -- one call for the
+        whole cohort.  ``bags``: a list of [n_b, P] tile embeddings (one per slide), ``(embeddings [N, P], offsets [S + 1])`` or
+        ``(embeddings [N, P], slide_ids [N])`` (slides in ``np.unique`` order); numpy or torch, un-normalised as ``encode_images``
+        returns them: a copy is L2-normalised on the device.  ``classes_or_prototypes``: class names / lists of synonyms
+        (``class_prototypes`` with ``templates``), or a ready float [C, P] array used as given; at most 64 classes.  ``scale`` None:
+        the model's ``exp(logit_scale)``.  Returns a dict of numpy arrays: ``pooled`` float32 [S, nks, C] (NaN for a slide without
+        tiles), ``pred`` int32 [S, nks] (-1 for such a slide), ``ks``, and with ``return_top_tiles`` = R <= ks[-1] ``top_tiles`` int64
+        [S, C, R], the best tiles per slide and class (``bags.slide_zero_shot`` says what they index)."""
+        from .bags import slide_zero_shot
+        if scale is None:
+            scale = float(np.exp(float(self.model.logit_scale)))
+        return slide_zero_shot(self.model.engine, bags, self._prototypes(classes_or_prototypes, templates), ks=ks, scale=float(scale),
+                               return_top_tiles=return_top_tiles)
+
+    def region_zero_shot(self, region, classes_or_prototypes, ks=(1, 5, 10, 50, 100), templates=("{}",), scale: Optional[float] = None,
+                         return_top_tiles: int = 10, **encode_region_kwargs) -> dict:
+        """(extension) ``encode_region`` (its keyword arguments pass through), then ``slide_zero_shot`` with the region's kept tiles as
+        ONE bag.  Returns what ``slide_zero_shot`` returns (S = 1; ``return_top_tiles`` is lowered to ks[-1]), plus ``top_coords`` int64
+        [C, R, 2] -- the (y, x) of the top tiles' top-left pixels, -1 where there are fewer tiles -- and ``region``, the
+        ``RegionEmbeddings``.  A region without tissue launches nothing: NaN ``pooled``, ``pred`` -1."""
+        from .bags import check_ks
+        kv = check_ks(ks, "region_zero_shot")
+        R = min(int(return_top_tiles), int(kv[-1]))
+        protos = self._prototypes(classes_or_prototypes, templates)
+        reg = self.encode_region(region, **encode_region_kwargs)
+        n_classes = int(protos.shape[0])
+        if reg.embeddings.shape[0] == 0:
+            res = {"pooled": np.full((1, kv.size, n_classes), np.nan, np.float32), "pred": np.full((1, kv.size), -1, np.int32),
+                   "ks": tuple(int(k) for k in kv)}
+            if R:
+                res["top_tiles"] = np.full((1, n_classes, R), -1, np.int64)
+        else:
+            res = self.slide_zero_shot((reg.embeddings, np.array([0, reg.embeddings.shape[0]], np.int32)), protos, ks=kv, scale=scale,
+                                       return_top_tiles=R)
+        if R:
+            top = res["top_tiles"][0]
+            res["top_coords"] = np.where((top >= 0)[..., None], reg.coords[np.maximum(top, 0)], -1) if len(reg.coords) else \
+                np.full((n_classes, R, 2), -1, np.int64)
+        res["region"] = reg
+        return res
+
     def encode_views(self, images, batch_size: int, views: int = 8, transform: str = "d4", seed: int = 0, reduce: Optional[str] = None,
                      return_params: bool = False):
         """(extension) Embeddings of ``views`` augmented views of every tile, the views built on the GPU (augment.py; Pillow-exact

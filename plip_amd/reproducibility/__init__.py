@@ -8,6 +8,7 @@ reproducibility/embedders/plip.py   ``CLIPEmbedder``   :class:`embedders.CLIPEmb
 reproducibility/embedders/factory.py                   :class:`embedders.EmbedderFactory`
 reproducibility/utils/cacher.py                        :mod:`cacher` (same file names and .npy bytes)
 reproducibility/evaluation/zero_shot/zero_shot.py      :class:`evaluation.ZeroShotClassifier`
+(no counterpart: the same head over slides)            :class:`evaluation.SlideZeroShotClassifier`
 reproducibility/evaluation/retrieval/retrieval.py      :class:`evaluation.ImageRetrieval`
 reproducibility/evaluation/linear_probing/             :class:`linear_probe.LinearProber`
 reproducibility/metrics.py                             :mod:`metrics`
@@ -21,7 +22,7 @@ loss-and-gradient passes and predictions all run in libplipmi.so on the GPU; onl
 from .cacher import (cache_hit_or_miss, cache_hit_or_miss_raw_filename, cache_numpy_object,  # noqa: F401
                      cache_numpy_object_raw_filename, get_cache_name, get_savepath)
 from .embedders import CLIPEmbedder, EmbedderFactory  # noqa: F401
-from .evaluation import ImageRetrieval, ZeroShotClassifier  # noqa: F401
+from .evaluation import ImageRetrieval, SlideZeroShotClassifier, ZeroShotClassifier  # noqa: F401
 from .linear_probe import LinearProber  # noqa: F401
 from .metrics import eval_metrics, retrieval_metrics  # noqa: F401
 from .softmax_probe import SoftmaxProber  # noqa: F401
